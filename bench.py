@@ -12,10 +12,18 @@ RCCL all-reduce of all gradients (overlapped with backward), in-graph LR schedul
 fused optimizer update (+ bf16 weight refresh). Weak scaling: per-GPU batch fixed.
 Data: one synthetic batch resident on each GPU; weights random-init.
 
+A plain run sets up, warms up, times the steps and prints one JSON result line. --full adds what
+takes work of its own after the timed steps (multi-rank runs: an instrumented step for the
+collectives' exposed time, the replicas-in-sync check, the all-reduce bandwidth probe).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): the
+step's returned sums, and fixed seeded samples of the gradients and of the updated fp32 weights.
+Weights and data are seeded, so two runs with the same arguments see identical inputs.
+
 Launch: with --gpus N > 1 and no WORLD_SIZE in the environment, this process starts N rank
 processes itself (torch.distributed.run on 127.0.0.1, before it touches any GPU), relays their
-output and exits non-zero unless rank 0 reports an N-rank process group whose replicas stayed
-bit-identical. Under an external launcher (WORLD_SIZE set) every rank runs the step directly.
+output and exits non-zero unless rank 0 reports an N-rank process group (with --full: whose
+replicas stayed bit-identical). Under an external launcher (WORLD_SIZE set) every rank runs the
+step directly.
 
 --model bert runs BASELINE config 4 instead (BERT-Large seq 512 pre-training, MLM+NSP,
 dropout on, LAMB; sequences/sec). --model mlp runs the reference's own workload (the
@@ -174,6 +182,34 @@ def build_mlp(args, dev, rank, world):
     return step, B, info
 
 
+DUMP_SAMPLE = 4 << 20  # elements kept of an array larger than this (16 MB as float32)
+
+
+def dump_outputs(path, last, params):
+    """Write what the last timed step handed its caller as path/<name>.npy (float32): the
+    returned sums, the gradients it left in params.grad and the fp32 weights its optimizer
+    update produced. An array of more than DUMP_SAMPLE elements is sampled at fixed positions
+    (seeded draw, sorted, the same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if isinstance(last, torch.Tensor):
+        arrays["sums"] = last
+    elif isinstance(last, dict):
+        arrays.update({"sums_%s" % k: torch.as_tensor(v) for k, v in last.items()})
+    elif last is not None:
+        arrays.update({"sums_%d" % i: torch.as_tensor(v) for i, v in enumerate(last)})
+    if params is not None:
+        arrays["grad"] = params.grad
+        arrays["weights"] = params.master
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(20240229).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -234,6 +270,13 @@ def main():
     ap.add_argument("--compress-bf16", action="store_true", help="all-reduce gradients in bf16")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp8"], help="ResNet conv forward precision")
     ap.add_argument("--optimizer", default="momentum", choices=["momentum", "lamb"], help="ResNet optimizer")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that take work of their own after the timed "
+                         "steps (multi-rank: instrumented collectives step, replicas-in-sync check, all-reduce "
+                         "bandwidth probe)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (returned sums, samples of the gradients and "
+                         "of the updated weights) as DIR/<name>.npy")
     ap.add_argument("--run-config", default=None,
                     help="JSON/YAML RunConfig file (utils/run_config.py); its fields override the flags above")
     args = ap.parse_args()
@@ -395,13 +438,17 @@ def main():
         dist.barrier()
     sync()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        run()
+        last = run()
     sync()
     if world > 1:
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before anything below runs another step or touches the weights
+        dump_outputs(args.dump_outputs, last, getattr(step, "params", None))
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     per_rank = [elapsed]
     if world > 1:
@@ -411,9 +458,9 @@ def main():
     elapsed = max(per_rank)
     red = getattr(step, "reducer", None)
     comm_stats = None
-    if red is not None and world > 1 and red.time_next_step():
-        # one extra (untimed, eager) step with the collectives instrumented: busy time on the
-        # communicator stream and the part of it the backward did not hide
+    if args.full and red is not None and world > 1 and red.time_next_step():
+        # --full: one extra (untimed, eager) step with the collectives instrumented: busy time on
+        # the communicator stream and the part of it the backward did not hide
         if graph is None:
             run()
         elif prio is not None:
@@ -423,12 +470,13 @@ def main():
             step()
         sync()
         comm_stats = red.comm_stats()
-    sums = step() if graph is None else out
+    # the loss of the last timed step (a replayed graph's outputs live in fixed buffers)
+    sums = last if last is not None else out if graph is not None else step()
     loss = float(sums[0])
-    # replicas must hold identical weights after synchronous data-parallel steps
+    # --full: replicas must hold identical weights after synchronous data-parallel steps
     params = getattr(step, "params", None)
     replicas_in_sync = None
-    if world > 1 and params is not None:
+    if args.full and world > 1 and params is not None:
         # BN moving statistics are per replica (TF SyncOnRead): average them as a checkpoint
         # save would, then every variable must be bit-identical across ranks
         from tensorflow_train_distributed_amd.parallel.collective import sync_on_read_mean_
@@ -449,12 +497,12 @@ def main():
             if rank == 0:
                 print("bench: %d of %d variables differ across replicas, e.g. %s" % (len(bad), len(names), bad[:8]),
                       file=sys.stderr)
-    # collective evidence for the scaling run: RCCL bus bandwidth of the gradient all-reduce at
-    # the bucket sizes the reducer uses and at the whole gradient buffer (after the timed region,
-    # on scratch copies: it does not touch the weights)
+    # --full: collective evidence for the scaling run: RCCL bus bandwidth of the gradient all-reduce
+    # at the bucket sizes the reducer uses and at the whole gradient buffer (after the timed
+    # region, on scratch copies: it does not touch the weights)
     probe = None
     red = getattr(step, "reducer", None)
-    if world > 1 and red is not None and not on_cpu and backend == "nccl":
+    if args.full and world > 1 and red is not None and not on_cpu and backend == "nccl":
         probe = []
         nbytes_all = red.flat.numel * 4
         sizes = sorted({min(nbytes_all, 4 << 20), min(nbytes_all, int(args.bucket_mb * (1 << 20))), nbytes_all})
@@ -526,6 +574,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms, 3),
             "higher_is_better": True,
             "scaling": "weak",

@@ -149,10 +149,16 @@ def _src_hash(kind):
 
 def _ensure(kind, lib, builder, force=False):
     """Build `lib` unless its stamp matches the current source hash (mtime-independent, so
-    a snapshot copied to another machine does not rebuild). Serialised across processes."""
-    os.makedirs(_LIBDIR, exist_ok=True)
+    a snapshot copied to another machine does not rebuild). Serialised across processes.
+    An up-to-date library is used as it is, without the lock: a tree built by one user can be
+    run by another who may not write to it."""
     stamp = lib + ".stamp"
     want = _src_hash(kind)
+    if not force and os.path.exists(lib) and os.path.exists(stamp):
+        with open(stamp) as fh:
+            if fh.read().strip() == want:
+                return lib
+    os.makedirs(_LIBDIR, exist_ok=True)
     with open(os.path.join(_LIBDIR, ".build.lock"), "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         try:

@@ -154,7 +154,7 @@ def test_bench_self_launches_n_ranks(n):
     env.pop("WORLD_SIZE", None)
     env["CUDA_VISIBLE_DEVICES"] = ""
     p = subprocess.run([sys.executable, "bench.py", "--model", "mlp", "--device", "cpu", "--gpus", str(n),
-                        "--steps", "3", "--warmup", "1"], cwd=REPO, env=env, stdout=subprocess.PIPE,
+                        "--steps", "3", "--warmup", "1", "--full"], cwd=REPO, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -165,6 +165,40 @@ def test_bench_self_launches_n_ranks(n):
     assert r["config"]["global_batch"] == 128 * n
     assert r["dist"]["allreduce_bytes_per_step"] >= 183685 * 4
     assert r["value"] > 0 and r["ms_per_step"] > 0
+
+
+def _bench_cpu(*extra):
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    p = subprocess.run([sys.executable, "bench.py", "--model", "mlp", "--device", "cpu", "--gpus", "1", *extra],
+                       cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_is_reproducible_and_steps_count(tmp_path):
+    """--dump-outputs writes the last timed step's sums, gradients and updated weights as float32
+    .npy; two runs with the same arguments write identical arrays (seeded weights and data); one
+    more timed step gives other weights, so --steps sets the number of steps that run."""
+    import numpy as np
+    a, b, c = (str(tmp_path / n) for n in "abc")
+    ra = _bench_cpu("--steps", "2", "--warmup", "1", "--dump-outputs", a)
+    _bench_cpu("--steps", "2", "--warmup", "1", "--dump-outputs", b)
+    rc = _bench_cpu("--steps", "3", "--warmup", "1", "--dump-outputs", c, "--full")
+    assert ra["steps"] == 2 and rc["steps"] == 3 and ra["ms_per_step"] > 0 and ra["dtype"] == "fp32"
+    assert sorted(os.listdir(a)) == ["grad.npy", "sums.npy", "weights.npy"]
+    total = 0
+    for name in os.listdir(a):
+        xa, xb = np.load(os.path.join(a, name)), np.load(os.path.join(b, name))
+        assert xa.dtype == np.float32 and np.isfinite(xa).all() and np.count_nonzero(xa)
+        assert np.array_equal(xa, xb), name
+        total += xa.nbytes
+    assert total <= 64 << 20
+    assert np.load(os.path.join(a, "sums.npy"))[0] == np.float32(ra["config"]["final_loss"])
+    assert not np.array_equal(np.load(os.path.join(a, "weights.npy")), np.load(os.path.join(c, "weights.npy")))
 
 
 def _tape_worker(rank, world, store, q, clip=None):

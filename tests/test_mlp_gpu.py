@@ -180,8 +180,8 @@ def test_two_gpu_ranks_over_gloo_stay_in_sync(model):
     env.pop("WORLD_SIZE", None)
     env["TTD_DIST_BACKEND"] = "gloo"
     extra = ["--batch", "16", "--image-size", "64"] if model == "resnet50" else []
-    p = subprocess.run([sys.executable, "bench.py", "--model", model, "--gpus", "2", "--steps", "2", "--warmup", "1"]
-                       + extra, cwd=repo, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+    p = subprocess.run([sys.executable, "bench.py", "--model", model, "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--full"] + extra, cwd=repo, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
