@@ -8,9 +8,14 @@
 // are fp32 [B*H][S]. Scores live in the log2 domain: s2 = (q.k) * log2(e)/sqrt(64),
 // P = exp2(s2 - lse2).
 //
-// Options: per-batch key lengths (keys >= len masked), and attention-probability dropout
-// whose keep mask is a counter hash of (seed, step, site, (b*H+h, q, key)) — regenerated
-// identically in both backward kernels, never stored.
+// Options: per-batch key lengths (keys >= len masked), causal masking (query q attends keys
+// k <= q; fwd, bwd_q and bwd_kv skip the tiles above the diagonal: 20 of 32 at S = 512), and
+// attention-probability dropout whose keep mask is a counter hash of (seed, step, site,
+// (b*H+h, q, key)) — regenerated identically in both backward kernels, never stored; the hash
+// inputs are absolute indices, so a causal run keeps what a bidirectional run keeps.
+// Causal at BERT-Large b128 (S = 512, p = 0.1): fwd 198 us against 277 us bidirectional, bwd_q +
+// bwd_kv 577 us against 782 us — with the rotated block order of causal_block(); in natural or
+// heavy-first order the causal kernels gain 6 % at most (profiles/attn_causal_bench.txt).
 //
 // Kernels (4 waves / workgroup, XCD-aware block order so the Q-blocks of one head share an
 // L2):
@@ -67,6 +72,7 @@ struct AttnParams {
   float drop_scale;    // 1 / (1 - p)
   const long long* rng;
   uint32_t site;
+  int order;           // causal block order within a head: causal_block()
 };
 
 __device__ __forceinline__ uint4 ldg16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
@@ -111,15 +117,47 @@ struct TileLoader {
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// Causal workgroups do unequal work (block b of a head streams 2b + 2 tiles in fwd / bwd_q, and
+// 2 (nblk - b) in bwd_kv), and the nblk blocks of a head stay adjacent in the grid (they share
+// K / V or Q / dO in one XCD's L2). Which block the j-th work item of head bh takes:
+//   order 0  natural (j);
+//   order 1  heavy first: the longest block of each head first. Measured no better than natural,
+//            and both about as slow as if every block were the longest: the grid then has period
+//            nblk, workgroups reach the CUs round-robin, so a CU keeps drawing the same block
+//            index and the CUs that draw the long one set the kernel's time;
+//   order 2  rotated: j plus the base-4 digit sum of bh. Over every power-of-two stride of the
+//            grid the block index then cycles evenly, so every CU gets the same mix.
+// (profiles/attn_causal_bench.txt)
+__device__ __forceinline__ int causal_block(int j, int bh, int nblk, int order, bool long_last) {
+  if (order == 2) {
+    uint32_t x = static_cast<uint32_t>(bh);
+    x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+    x = (x + (x >> 4)) & 0x0f0f0f0fu;
+    x = (x * 0x01010101u) >> 24;  // sum of the base-4 digits (<= 48)
+    return static_cast<int>((static_cast<uint32_t>(j) + x) % static_cast<uint32_t>(nblk));
+  }
+  return order == 1 && long_last ? nblk - 1 - j : j;
+}
+
 // ------------------------------------------------------------------------------ forward
 // (launch_bounds(256, 4) — 128 VGPRs, 4 waves / SIMD instead of 3, 10-12 spilled — measured
 // 10-18 % slower at BERT-Large b128: the spills land in the loop)
-template <bool DROP>
+//
+// CAUSAL (query q attends keys k <= q, and k < len): only key tiles kt <= 2 qblk + 1 are streamed;
+// the per-element compare runs on the tiles that cross the wave's diagonal only (wave-uniform,
+// as the len mask is block-uniform), and a wave whose 32 rows all lie below a tile's first key
+// skips the tile's MFMA / softmax work (it still moves its share of the next tile and meets the
+// barrier). Masked scores are -inf BEFORE the row max, so a masked key adds exactly nothing to
+// m, l, O; and the running max moves per row (not for every row of a wave whose ballot fired), so
+// a row's result does not depend on keys that only other rows of its wave may see.
+template <bool DROP, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int qblocks = P.S / QBLK;
   const int t = tile::xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = t / qblocks, qblk = t - bh * qblocks;
+  const int bh = t / qblocks;
+  int qblk = t - bh * qblocks;
+  if constexpr (CAUSAL) qblk = causal_block(qblk, bh, qblocks, P.order, true);
   const int b = bh / P.H, h = bh - b * P.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
@@ -146,7 +184,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     for (int db = 0; db < 4; ++db) o[qb][db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
-  const int ntiles = (len + KT - 1) / KT;
+  int ntiles = (len + KT - 1) / KT;
+  if constexpr (CAUSAL) ntiles = min(ntiles, 2 * qblk + 2);
   if (ntiles > 0) {
     lk.load(0, len);
     lv.load(0, len);
@@ -163,93 +202,111 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     }
     const char* sK = smem + cur * 2 * TILE_BYTES;
     const char* sV = sK + TILE_BYTES;
-    // ---- S^T tile: lane holds keys kb*16 + 4g + i for query qb*16 + i16
-    f32x4_t s[2][4];
+    // CAUSAL: every key of the tile lies above every row of this wave (wave-uniform)
+    if (!CAUSAL || kt * KT <= q0 + 31) {
+      // ---- S^T tile: lane holds keys kb*16 + 4g + i for query qb*16 + i16
+      f32x4_t s[2][4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      const bf16x8_t k0 = rd_row(sK, kb * 16 + i16, g);
-      const bf16x8_t k1 = rd_row(sK, kb * 16 + i16, 4 + g);
+      for (int kb = 0; kb < 4; ++kb) {
+        const bf16x8_t k0 = rd_row(sK, kb * 16 + i16, g);
+        const bf16x8_t k1 = rd_row(sK, kb * 16 + i16, 4 + g);
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+          s[qb][kb] = mfma(k0, qf[qb][0], f32x4_t{0.f, 0.f, 0.f, 0.f});
+          s[qb][kb] = mfma(k1, qf[qb][1], s[qb][kb]);
+        }
+      }
+      const int kbase = kt * KT;
+      if (kbase + KT > len) {
+        // (block-uniform: only the last key tile of a padded sequence; the full tiles run no
+        // per-element compare / select — the kernel is VALU-bound, profiles/r3_bert_*_pmc_*)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+          for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (kbase + kb * 16 + 4 * g + i >= len) s[qb][kb][i] = -INFINITY;
+      }
+      if constexpr (CAUSAL) {
+        if (kbase + KT - 1 > q0) {
+          // (wave-uniform: the tile crosses this wave's diagonal; key > query <=> kb*16 + i - qb*16
+          // > qd = query - (kbase + 4g), constants against one lane value)
+          const int qd = q0 + i16 - kbase - 4 * g;
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+              for (int i = 0; i < 4; ++i)
+                if (kb * 16 + i - qb * 16 > qd) s[qb][kb][i] = -INFINITY;
+        }
+      }
+      bf16x8_t pf[2][2];
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb) {
-        s[qb][kb] = mfma(k0, qf[qb][0], f32x4_t{0.f, 0.f, 0.f, 0.f});
-        s[qb][kb] = mfma(k1, qf[qb][1], s[qb][kb]);
-      }
-    }
-    const int kbase = kt * KT;
-    if (kbase + KT > len) {
-      // (block-uniform: only the last key tile of a padded sequence; the full tiles run no
-      // per-element compare / select — the kernel is VALU-bound, profiles/r3_bert_*_pmc_*)
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
+        // max over the raw scores (scale > 0 commutes with max); the scale rides in the exp2 FMA
+        float mx = -INFINITY;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (kbase + kb * 16 + 4 * g + i >= len) s[qb][kb][i] = -INFINITY;
-    }
-    bf16x8_t pf[2][2];
+          for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[qb][kb][i]);
+        mx = tile::rows4_max(mx);
+        // lazy rescale: the running max moves (and O, l are rescaled) only when some row of the
+        // wave saw its max grow by more than 8 (log2 units) — otherwise P = exp2(s - m) stays
+        // below 2^8 (exact in fp32, in range for the bf16 P operand) and the 16 O multiplies and
+        // the alpha exp2 of the tile are skipped (wave-uniform branch; lse = m + log2 l either way)
+        const float mxs = mx * P.scale_log2;
+        float alpha = 1.f;
+        const bool grow = mxs > m[qb] + 8.f;
+        if (__builtin_amdgcn_ballot_w64(grow) != 0) {
+          float mnew = fmaxf(m[qb], mxs);
+          if constexpr (CAUSAL) mnew = grow ? mnew : m[qb];  // per row: alpha is exactly 1 elsewhere
+          alpha = fast_exp2(m[qb] - (mnew == -INFINITY ? 0.f : mnew));
+          m[qb] = mnew;
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      // max over the raw scores (scale > 0 commutes with max); the scale rides in the exp2 FMA
-      float mx = -INFINITY;
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[qb][kb][i]);
-      mx = tile::rows4_max(mx);
-      // lazy rescale: the running max moves (and O, l are rescaled) only when some row of the
-      // wave saw its max grow by more than 8 (log2 units) — otherwise P = exp2(s - m) stays
-      // below 2^8 (exact in fp32, in range for the bf16 P operand) and the 16 O multiplies and
-      // the alpha exp2 of the tile are skipped (wave-uniform branch; lse = m + log2 l either way)
-      const float mxs = mx * P.scale_log2;
-      float alpha = 1.f;
-      const bool grow = mxs > m[qb] + 8.f;
-      if (__builtin_amdgcn_ballot_w64(grow) != 0) {
-        const float mnew = fmaxf(m[qb], mxs);
-        alpha = fast_exp2(m[qb] - (mnew == -INFINITY ? 0.f : mnew));
-        m[qb] = mnew;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) o[qb][db] *= alpha;
-      }
-      const float msub = m[qb] == -INFINITY ? 0.f : m[qb];
-      float rs = 0.f;
-      const int qrow = q0 + qb * 16 + i16;
-      // keys kbase + kb*16 + 4g + i: pair kbase/2 + (kb >> 1)*16 + 4g + i, half kb & 1 — the
-      // hash input is a per-tile base plus constants
-      uint32_t hp[2][4] = {};
-      if constexpr (DROP) {
-        const uint32_t hbase = attn_row_term(static_cast<uint32_t>(bh * P.S + qrow)) +
-                               (static_cast<uint32_t>(kbase >> 1) + 4u * g) * kAttnPairMul;
-#pragma unroll
-        for (int kp = 0; kp < 2; ++kp)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) hp[kp][i] = attn_hash_input(key, hbase + (16u * kp + i) * kAttnPairMul);
-      }
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float p = fast_exp2(__builtin_fmaf(s[qb][kb][i], P.scale_log2, -msub));
-          rs += p;
-          float pd = p;
-          if constexpr (DROP) pd = attn_keep_half(hp[kb >> 1][i], kb & 1, P.drop_thr) ? p : 0.f;
-          s[qb][kb][i] = pd;
+          for (int db = 0; db < 4; ++db) o[qb][db] *= alpha;
         }
+        const float msub = m[qb] == -INFINITY ? 0.f : m[qb];
+        float rs = 0.f;
+        const int qrow = q0 + qb * 16 + i16;
+        // keys kbase + kb*16 + 4g + i: pair kbase/2 + (kb >> 1)*16 + 4g + i, half kb & 1 — the
+        // hash input is a per-tile base plus constants
+        uint32_t hp[2][4] = {};
+        if constexpr (DROP) {
+          const uint32_t hbase = attn_row_term(static_cast<uint32_t>(bh * P.S + qrow)) +
+                                 (static_cast<uint32_t>(kbase >> 1) + 4u * g) * kAttnPairMul;
+#pragma unroll
+          for (int kp = 0; kp < 2; ++kp)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hp[kp][i] = attn_hash_input(key, hbase + (16u * kp + i) * kAttnPairMul);
+        }
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float p = fast_exp2(__builtin_fmaf(s[qb][kb][i], P.scale_log2, -msub));
+            rs += p;
+            float pd = p;
+            if constexpr (DROP) pd = attn_keep_half(hp[kb >> 1][i], kb & 1, P.drop_thr) ? p : 0.f;
+            s[qb][kb][i] = pd;
+          }
+        }
+        rs = tile::rows4_sum(rs);
+        l[qb] = l[qb] * alpha + rs;
+        pf[qb][0] = pack_frag(s[qb][0], s[qb][1]);
+        pf[qb][1] = pack_frag(s[qb][2], s[qb][3]);
       }
-      rs = tile::rows4_sum(rs);
-      l[qb] = l[qb] * alpha + rs;
-      pf[qb][0] = pack_frag(s[qb][0], s[qb][1]);
-      pf[qb][1] = pack_frag(s[qb][2], s[qb][3]);
+      // ---- O += P V
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int db = 0; db < 4; ++db) {
+          const bf16x8_t vf = rd_col(sV, ks * 32, ks * 32 + 16, db * 16, lane);
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb) o[qb][db] = mfma(vf, pf[qb][ks], o[qb][db]);
+        }
     }
-    // ---- O += P V
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const bf16x8_t vf = rd_col(sV, ks * 32, ks * 32 + 16, db * 16, lane);
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) o[qb][db] = mfma(vf, pf[qb][ks], o[qb][db]);
-      }
     if (nxt) {
       lk.store(smem + (cur ^ 1) * 2 * TILE_BYTES);
       lv.store(smem + (cur ^ 1) * 2 * TILE_BYTES + TILE_BYTES);
@@ -289,13 +346,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 // results, for attributing the kernel's time; bit 3 writes per-workgroup clock stamps (entry,
 // prologue done, loop done, exit as s_memtime; entry / exit as s_memrealtime) over dV as
 // int64[grid][8] instead of dV (tools/attn_kv_stamps.py).
-template <bool DROP, int MODE = 0>
+//
+// CAUSAL (MODE 0 only): the query-tile loop starts at qt0 = 2 kblk (even, so the two-buffer trip
+// structure holds); the two tiles of the first trip cross the block's diagonal and run the
+// diagonal form of the tile body: queries below the key get P = 0 and dS = 0 in pds, and a wave
+// (32 keys from k0) whose keys all lie above the tile's last query skips the tile (no MFMA /
+// softmax work, only its share of the next tile's staging and the barrier). Every later trip
+// runs today's unmasked body. Block order: causal_block().
+template <bool DROP, int MODE = 0, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   constexpr int BUF = 2 * TILE_BYTES + 2 * KT * 4;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int kblocks = P.S / QBLK;
   const int t = tile::xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = t / kblocks, kblk = t - bh * kblocks;
+  const int bh = t / kblocks;
+  int kblk = t - bh * kblocks;
+  if constexpr (CAUSAL) kblk = causal_block(kblk, bh, kblocks, P.order, false);
   const int b = bh / P.H, h = bh - b * P.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
@@ -379,7 +445,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
           for (int i = 0; i < 4; ++i)
             hh[u][i] = attn_hash_input(key, hrow + static_cast<uint32_t>((2 * hq + u) * 16 + i) * 0x9E3779B1u);
     };
-    auto pds = [&](const float* sL, const uint32_t (&hq_hash)[2][4], int hq, f32x4_t (&sc)[4][2], f32x4_t (&dp)[4][2]) {
+    // DIAG (causal, diagonal tile): query < key <=> qb*16 + i - kb*16 < kd, kd = key - (tile's
+    // first query + 4g) of the lane's kb = 0 key; the score is -inf there, so P_d = 0 and dS = 0
+    // exactly (masking the score, not p, also keeps this form free of spills).
+    auto pds = [&](const float* sL, const uint32_t (&hq_hash)[2][4], int hq, f32x4_t (&sc)[4][2], f32x4_t (&dp)[4][2],
+                   auto diag_c, int kd) {
+      constexpr bool DIAG = decltype(diag_c)::value;
       const float* sDel = sL + KT;
 #pragma unroll
       for (int qb = 2 * hq; qb < 2 * hq + 2; ++qb)
@@ -390,7 +461,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
           const uint32_t hh = hq_hash[qb - 2 * hq][i];
 #pragma unroll
           for (int kb = 0; kb < 2; ++kb) {
-            const float p = fast_exp2(__builtin_fmaf(sc[qb][kb][i], P.scale_log2, -lse2));
+            float sv = sc[qb][kb][i];
+            if constexpr (DIAG) sv = qb * 16 + i - kb * 16 < kd ? -INFINITY : sv;
+            const float p = fast_exp2(__builtin_fmaf(sv, P.scale_log2, -lse2));
             const float dpv = dp[qb][kb][i];
             if constexpr (DROP) {
               const float pd = attn_keep_half(hh, kb, P.drop_thr) ? p : 0.f;
@@ -427,60 +500,80 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     // immediate); the next tile's global loads are in flight meanwhile and stored into the other
     // buffer at the end
     f32x4_t sc[4][2], dp[4][2];
-    auto tile = [&](int qt, auto bufi_c) {
+    // diag_c (causal): a tile of the diagonal trip — masked in pds, and skipped by a wave whose
+    // keys all lie above the tile's last query (wave-uniform)
+    auto tile = [&](int qt, auto bufi_c, auto diag_c) {
       constexpr int BUFI = decltype(bufi_c)::value;
+      constexpr bool DIAG = decltype(diag_c)::value;
+      constexpr int DV = DIAG ? 2 : 0;  // the mask's compare and select per element, per MFMA slot
+      const int kd = k0 + i16 - qt * KT - 4 * g;
       const bool nxt = qt + 1 < ntiles && !(MODE & 2);
       if (nxt) load(qt + 1);
-      const char* sQ = smem + BUFI * BUF;
-      const float* sL = reinterpret_cast<const float*>(sQ + 2 * TILE_BYTES);
-      const uint32_t hrow = DROP ? attn_row_term(static_cast<uint32_t>(bh * P.S + qt * KT + 4 * g)) +
-                                       (static_cast<uint32_t>(k0 >> 1) + i16) * kAttnPairMul
-                                 : 0u;
-      // four phases, MFMA work beside independent VALU work of the same wave, spread one MFMA per
-      // few VALU instructions by sched_group_barrier:
-      //   S/dP(rows 0-31) + hashes(rows 0-31) | S/dP(rows 32-63) + P/dS(rows 0-31) + hashes(rows
-      //   32-63) | dV/dK(rows 0-31) + P/dS(rows 32-63) | dV/dK(rows 32-63)
-      uint32_t h0[2][4] = {}, h1[2][4] = {};
-      sdp(sQ, 0, sc, dp);
-      hashes(hrow, 0, h0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+      if (!DIAG || __builtin_amdgcn_readfirstlane(k0) <= qt * KT + KT - 1) {
+        const char* sQ = smem + BUFI * BUF;
+        const float* sL = reinterpret_cast<const float*>(sQ + 2 * TILE_BYTES);
+        const uint32_t hrow = DROP ? attn_row_term(static_cast<uint32_t>(bh * P.S + qt * KT + 4 * g)) +
+                                         (static_cast<uint32_t>(k0 >> 1) + i16) * kAttnPairMul
+                                   : 0u;
+        // four phases, MFMA work beside independent VALU work of the same wave, spread one MFMA per
+        // few VALU instructions by sched_group_barrier:
+        //   S/dP(rows 0-31) + hashes(rows 0-31) | S/dP(rows 32-63) + P/dS(rows 0-31) + hashes(rows
+        //   32-63) | dV/dK(rows 0-31) + P/dS(rows 32-63) | dV/dK(rows 32-63)
+        uint32_t h0[2][4] = {}, h1[2][4] = {};
+        sdp(sQ, 0, sc, dp);
+        hashes(hrow, 0, h0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
 #pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, DROP ? 3 : 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      sdp(sQ, 1, sc, dp);
-      if constexpr (!(MODE & 1)) pds(sL, h0, 0, sc, dp);
-      hashes(hrow, 1, h1);
-      __builtin_amdgcn_sched_group_barrier(0x100, 12, 1);
+        for (int k = 0; k < 16; ++k) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, DROP ? 3 : 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        sdp(sQ, 1, sc, dp);
+        if constexpr (!(MODE & 1)) pds(sL, h0, 0, sc, dp, diag_c, kd);
+        hashes(hrow, 1, h1);
+        __builtin_amdgcn_sched_group_barrier(0x100, 12, 1);
 #pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-        __builtin_amdgcn_sched_group_barrier(0x002, DROP ? 10 : 6, 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      pv(sQ, 0, sc, dp);
-      if constexpr (!(MODE & 1)) pds(sL, h1, 1, sc, dp);
-      __builtin_amdgcn_sched_group_barrier(0x100, 20, 2);
-      __builtin_amdgcn_sched_group_barrier(0x002, 8, 2);
+        for (int k = 0; k < 16; ++k) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
+          __builtin_amdgcn_sched_group_barrier(0x002, (DROP ? 10 : 6) + DV, 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        pv(sQ, 0, sc, dp);
+        if constexpr (!(MODE & 1)) pds(sL, h1, 1, sc, dp, diag_c, kd);
+        __builtin_amdgcn_sched_group_barrier(0x100, 20, 2);
+        __builtin_amdgcn_sched_group_barrier(0x002, 8, 2);
 #pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 2);
-        __builtin_amdgcn_sched_group_barrier(0x002, DROP ? 8 : 5, 2);
+        for (int k = 0; k < 16; ++k) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 2);
+          __builtin_amdgcn_sched_group_barrier(0x002, (DROP ? 8 : 5) + DV, 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        pv(sQ, 1, sc, dp);
       }
-      __builtin_amdgcn_sched_barrier(0);
-      pv(sQ, 1, sc, dp);
       if (nxt) store(smem + (BUFI ^ 1) * BUF);
       if constexpr (!(MODE & 4)) __syncthreads();
     };
-    load(0);
+    using std::integral_constant;
+    using std::false_type;
+    using std::true_type;
+    const int qt0 = CAUSAL ? 2 * kblk : 0;
+    load(qt0);
     store(smem);
     __syncthreads();
     if constexpr ((MODE & 8) != 0) stamp[1] = __builtin_amdgcn_s_memtime();
-    for (int qt = 0; qt < ntiles; qt += 2) {  // ntiles is even
-      tile(qt, std::integral_constant<int, 0>{});
-      tile(qt + 1, std::integral_constant<int, 1>{});
+    int qt = qt0;
+    if constexpr (CAUSAL) {
+      // the diagonal trip: waves 0, 1 (keys 0-63 of the block) mask in tile qt0 (and see all of
+      // tile qt0 + 1: its compares never hit); waves 2, 3 (keys 64-127) skip tile qt0 and mask in
+      // tile qt0 + 1
+      tile(qt, integral_constant<int, 0>{}, true_type{});
+      tile(qt + 1, integral_constant<int, 1>{}, true_type{});
+      qt += 2;
+    }
+    for (; qt < ntiles; qt += 2) {  // ntiles - qt is even
+      tile(qt, integral_constant<int, 0>{}, false_type{});
+      tile(qt + 1, integral_constant<int, 1>{}, false_type{});
     }
     if constexpr ((MODE & 8) != 0) stamp[2] = __builtin_amdgcn_s_memtime();
   }
@@ -516,12 +609,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 }
 
 // ------------------------------------------------------------------------------ bwd dQ
-template <bool DROP>
+// CAUSAL: as the forward — key tiles kt <= 2 qblk + 1 only; per wave a tile runs full, diagonal
+// (score -inf where key > query, before the exp2: P = 0 and dS = 0 exactly) or skipped.
+template <bool DROP, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int qblocks = P.S / QBLK;
   const int t = tile::xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = t / qblocks, qblk = t - bh * qblocks;
+  const int bh = t / qblocks;
+  int qblk = t - bh * qblocks;
+  if constexpr (CAUSAL) qblk = causal_block(qblk, bh, qblocks, P.order, true);
   const int b = bh / P.H, h = bh - b * P.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
@@ -568,7 +665,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   lk.init(P.k + tok0 * P.ldk + h * D, P.ldk, tid);
   lv.init(P.v + tok0 * P.ldv + h * D, P.ldv, tid);
   const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
-  const int ntiles = (len + KT - 1) / KT;
+  int ntiles = (len + KT - 1) / KT;
+  if constexpr (CAUSAL) ntiles = min(ntiles, 2 * qblk + 2);
   if (ntiles > 0) {
     lk.load(0, len);
     lv.load(0, len);
@@ -608,14 +706,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   // dS in place for key half hk. (DROP: lse2 / del carry the dropout scale, p is P / (1-p) — see
   // the prologue.) Keys >= len need no mask: their K rows are zero-filled in LDS, so whatever dS
   // they get adds nothing to dQ = dS K (and their S = 0, dP = 0 keep dS finite).
-  auto pds = [&](int hk, const uint32_t (&hp)[2][4], f32x4_t (&sc)[2][4], const f32x4_t (&dp)[2][4]) {
+  // DIAG (causal, diagonal tile): key > query <=> kb*16 + i - qb*16 > qd, qd = the lane's qb = 0
+  // query - (tile's first key + 4g).
+  auto pds = [&](int hk, const uint32_t (&hp)[2][4], f32x4_t (&sc)[2][4], const f32x4_t (&dp)[2][4], auto diag_c,
+                 int qd) {
+    constexpr bool DIAG = decltype(diag_c)::value;
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
       for (int kb = 2 * hk; kb < 2 * hk + 2; ++kb)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float p = fast_exp2(__builtin_fmaf(sc[qb][kb][i], P.scale_log2, -lse2[qb]));
+          float sv = sc[qb][kb][i];
+          if constexpr (DIAG) sv = kb * 16 + i - qb * 16 > qd ? -INFINITY : sv;
+          const float p = fast_exp2(__builtin_fmaf(sv, P.scale_log2, -lse2[qb]));
           const float dpv = dp[qb][kb][i];
           if constexpr (DROP) {
             const float pd = attn_keep_half(hp[qb][i], kb & 1, P.drop_thr) ? p : 0.f;
@@ -641,21 +745,34 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   // 32-63) + dS(keys 0-31) | dQ(keys 0-31) + dS(keys 32-63) | dQ(keys 32-63)
   int cur = 0;
   f32x4_t sc[2][4], dp[2][4];
-  auto tile = [&](int kt) {
+  // FORM (causal): 0 full tile, 1 diagonal tile, 2 skipped by this wave
+  auto tile = [&](int kt, auto form_c) {
+    constexpr int FORM = decltype(form_c)::value;
+    const std::integral_constant<bool, FORM == 1> diag_c{};
     const bool nxt = kt + 1 < ntiles;
     if (nxt) {
       lk.load((kt + 1) * KT, len);
       lv.load((kt + 1) * KT, len);
     }
+    if constexpr (FORM == 2) {
+      if (nxt) {
+        lk.store(smem + (cur ^ 1) * 2 * TILE_BYTES);
+        lv.store(smem + (cur ^ 1) * 2 * TILE_BYTES + TILE_BYTES);
+      }
+      __syncthreads();
+      cur ^= 1;
+      return;
+    }
     const char* sK = smem + cur * 2 * TILE_BYTES;
     const int kbase = kt * KT;
+    const int qd = q0 + i16 - kbase - 4 * g;
     uint32_t h0[2][4] = {}, h1[2][4] = {};
     sdp(sK, 0, sc, dp);
     hashes(kbase, 0, h0);
     hashes(kbase, 1, h1);
     __builtin_amdgcn_sched_barrier(0);
     sdp(sK, 1, sc, dp);
-    pds(0, h0, sc, dp);
+    pds(0, h0, sc, dp, diag_c, qd);
     __builtin_amdgcn_sched_group_barrier(0x100, 8, 1);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -664,7 +781,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     }
     __builtin_amdgcn_sched_barrier(0);
     dqh(sK, 0, sc);
-    pds(1, h1, sc, dp);
+    pds(1, h1, sc, dp, diag_c, qd);
     __builtin_amdgcn_sched_group_barrier(0x100, 8, 2);
     __builtin_amdgcn_sched_group_barrier(0x002, 4, 2);
 #pragma unroll
@@ -681,7 +798,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     __syncthreads();
     cur ^= 1;
   };
-  for (int kt = 0; kt < ntiles; ++kt) tile(kt);
+  for (int kt = 0; kt < ntiles; ++kt) {
+    if constexpr (CAUSAL) {
+      // wave-uniform: all keys above all of the wave's rows | the tile crosses its diagonal
+      if (kt * KT > q0 + 31) tile(kt, std::integral_constant<int, 2>{});
+      else if (kt * KT + KT - 1 > q0) tile(kt, std::integral_constant<int, 1>{});
+      else tile(kt, std::integral_constant<int, 0>{});
+    } else {
+      tile(kt, std::integral_constant<int, 0>{});
+    }
+  }
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
     bf16_t* op = P.out + (tok0 + q0 + qb * 16 + i16) * P.ld_out + h * D + 4 * g;
@@ -928,6 +1054,18 @@ AttnParams make_params(int B, int H, int S, const int* seqlen, float p_drop, con
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Block order of the causal grids (causal_block()): rotated unless TTD_ATTN_CAUSAL_ORDER is
+// "natural" or "heavy" (kept for the A/B in profiles/attn_causal_bench.txt).
+int causal_order() {
+  static const int v = [] {
+    const char* e = getenv("TTD_ATTN_CAUSAL_ORDER");
+    if (e != nullptr && e[0] == 'n') return 0;
+    if (e != nullptr && e[0] == 'h') return 1;
+    return 2;
+  }();
+  return v;
+}
+
 }  // namespace
 }  // namespace ttdk
 
@@ -935,9 +1073,11 @@ using namespace ttdk;
 
 // Shapes: S % 128 == 0, head_dim 64, every ld % 8 == 0 and bases 16-B aligned (checked).
 // Returns hipErrorInvalidValue on violation (the Python wrapper raises).
-TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                              long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B, int H,
-                              int S, float p_drop, const long long* rng, unsigned site, hipStream_t st) {
+// causal != 0: query q attends keys k <= q (and k < seqlen[b]).
+TTDK_EXPORT int ttdk_attn_fwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                     long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
+                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
+                                     hipStream_t st) {
   if (S % QBLK || (ldq | ldk | ldv | ldo) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
       (p_drop > 0.f && !rng))
     return hipErrorInvalidValue;
@@ -945,9 +1085,22 @@ TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, l
   P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
   P.out = o; P.ld_out = ldo; P.lse = lse;
   dim3 grid(B * H * (S / QBLK)), block(256);
-  if (p_drop > 0.f) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, st, P);
-  else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, st, P);
+  if (causal) {
+    P.order = causal_order();
+    if (p_drop > 0.f) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, 0, st, P);
+  } else if (p_drop > 0.f) {
+    hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, st, P);
+  } else {
+    hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, st, P);
+  }
   return hipGetLastError();
+}
+
+TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                              long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B, int H,
+                              int S, float p_drop, const long long* rng, unsigned site, hipStream_t st) {
+  return ttdk_attn_fwd_causal(q, ldq, k, ldk, v, ldv, o, ldo, lse, seqlen, B, H, S, p_drop, rng, site, 0, st);
 }
 
 // Single-kernel backward (attn_bwd_fused_kernel) for S in {128, 256, 512}: opt-in
@@ -956,6 +1109,8 @@ TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, l
 // 177.2 ms — one workgroup per (b, h) holds 4 waves (the S = 512 dK^T / dV^T accumulators need
 // 256 AGPRs per lane: one wave per SIMD, LDS 145 KB: one workgroup per CU), too little
 // occupancy to hide the MFMA -> softmax dependencies; the 8-wave form spills 65 VGPRs.
+// The fused kernel has no causal form: a causal backward always runs the split kernels, whatever
+// this switch says.
 static int g_attn_fused = -1;
 static bool attn_fused_bwd() {
   if (g_attn_fused < 0) {
@@ -970,11 +1125,13 @@ TTDK_EXPORT int ttdk_attn_set_fused_bwd(int on) {
 }
 
 // dq/dk/dv may alias one fused [tokens, 3*H*64] buffer (different column offsets).
-TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                              long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
-                              const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk, long long lddk,
-                              bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int S, float p_drop,
-                              const long long* rng, unsigned site, hipStream_t st) {
+// causal != 0: the backward of ttdk_attn_fwd_causal(..., causal); split kernels only.
+TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                     long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
+                                     long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
+                                     bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
+                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
+                                     hipStream_t st) {
   if (S % QBLK || (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7 || !aligned16(q) || !aligned16(k) ||
       !aligned16(v) || !aligned16(o) || !aligned16(dout) || (p_drop > 0.f && !rng))
     return hipErrorInvalidValue;
@@ -983,7 +1140,7 @@ TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, l
   P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo; P.lddo = lddo;
   P.lse = const_cast<float*>(lse);
   P.delta = delta;
-  if (attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
+  if (!causal && attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
     // one workgroup per (batch, head): dQ, dK, dV in one pass (attn_bwd_fused_kernel)
     P.out = dq; P.ld_out = lddq; P.out2 = dk; P.ld_out2 = lddk; P.out3 = dv; P.ld_out3 = lddv;
     const dim3 g1(B * H);
@@ -1004,6 +1161,15 @@ TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, l
   dim3 grid(B * H * (S / QBLK)), block(256);
   // dQ first: it computes delta (rowsum dO . O) on the way and stores it for dK / dV
   P.out = dq; P.ld_out = lddq; P.out2 = nullptr;
+  if (causal) {
+    P.order = causal_order();
+    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_q_kernel<true, true>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((attn_bwd_q_kernel<false, true>), grid, block, 0, st, P);
+    P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
+    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, true>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, true>), grid, block, 0, st, P);
+    return hipGetLastError();
+  }
   if (p_drop > 0.f) hipLaunchKernelGGL(attn_bwd_q_kernel<true>, grid, block, 0, st, P);
   else hipLaunchKernelGGL(attn_bwd_q_kernel<false>, grid, block, 0, st, P);
   P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
@@ -1025,4 +1191,13 @@ TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, l
     hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid, block, 0, st, P);
   }
   return hipGetLastError();
+}
+
+TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                              long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
+                              const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk, long long lddk,
+                              bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int S, float p_drop,
+                              const long long* rng, unsigned site, hipStream_t st) {
+  return ttdk_attn_bwd_causal(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv,
+                              seqlen, B, H, S, p_drop, rng, site, 0, st);
 }

@@ -316,7 +316,10 @@ class Embedding(Layer):
 
 
 class MultiHeadAttention(Layer):
-    """Self-attention with fused QKV projection (head size 64 on the GPU flash kernels)."""
+    """Self-attention with fused QKV projection (head size 64 on the GPU flash kernels).
+    call(x, seqlen=None, training=True, use_causal_mask=False): keys >= seqlen[b] are masked;
+    use_causal_mask=True (Keras' name) lets position s attend positions <= s only, the
+    decoder-only / left-to-right form."""
     _default_name = "multi_head_attention"
 
     def __init__(self, num_heads, key_dim=64, dropout=0.0, name=None):
@@ -333,12 +336,12 @@ class MultiHeadAttention(Layer):
         self.add_weight("output/bias", (D,), "zeros", attr="out_bias")
         super().build(input_shape)
 
-    def call(self, x, seqlen=None, training=True, **kw):
+    def call(self, x, seqlen=None, training=True, use_causal_mask=False, **kw):
         inner = self.num_heads * self.key_dim
         qkv = N.dense(x, self.qkv_kernel, self.qkv_bias)
         q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
         a = N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
-                        self.dropout if training else 0.0, seqlen=seqlen)
+                        self.dropout if training else 0.0, seqlen=seqlen, causal=use_causal_mask)
         return N.dense(a, self.out_kernel, self.out_bias)
 
 

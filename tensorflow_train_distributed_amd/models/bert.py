@@ -51,6 +51,9 @@ class BertConfig:
     attention_probs_dropout_prob: float = 0.1
     layer_norm_eps: float = 1e-12
     initializer_range: float = 0.02
+    # causal self-attention (position s attends positions <= s): with labels on next-token
+    # positions the MLM head then trains a left-to-right language model
+    causal: bool = False
 
     @property
     def vocab_padded(self) -> int:
@@ -449,7 +452,7 @@ class BertPretraining:
             ao = torch.empty((Tk, H), dtype=bf, device=dev)
             lse = torch.empty((B * NH, S), dtype=torch.float32, device=dev)
             T.attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, lse, B, NH, S, seqlen=seqlen,
-                            p_drop=ad, rng=rng, site=site(l, 0))
+                            p_drop=ad, rng=rng, site=site(l, 0), causal=c.causal)
             nb = self._ln(l, "attention/output/dense/bias")
             proj = self._plain(ao, P.c[self._ln(l, "attention/output/dense/kernel")], P.var[nb], P.c[nb])
             y1, s1, m1, r1 = T.layernorm_fwd(proj, P.var[self._ln(l, "attention/output/LayerNorm/gamma")],
@@ -570,7 +573,7 @@ class BertPretraining:
             dqkv = torch.empty((Tk, 3 * H), dtype=bf, device=dev)
             T.attention_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, dao, lse, dqkv[:, :H],
                             dqkv[:, H:2 * H], dqkv[:, 2 * H:], B, NH, S, delta=delta, seqlen=seqlen, p_drop=ad,
-                            rng=rng, site=site(l, 0))
+                            rng=rng, site=site(l, 0), causal=c.causal)
             if self.ln_yield == 2:
                 flush_wgrads()  # (mode 2: the attention backward runs without side-stream GEMMs too)
             del dao, ao, qkv
@@ -623,6 +626,7 @@ class BertPretraining:
         if batch.seqlen is not None:
             ar = torch.arange(S, device=x.device)
             keymask = ar[None, :] < batch.seqlen[:, None].long()
+        tri = torch.ones((S, S), dtype=torch.bool, device=x.device).tril() if c.causal else None
         for l in range(L):
             p = lambda s, l=l: self._ln(l, s)  # noqa: E731
             q = lin(x, p("attention/self/query")).view(B, S, NH, 64).transpose(1, 2)
@@ -631,6 +635,8 @@ class BertPretraining:
             sc = q @ k.transpose(-1, -2) / 8.0
             if keymask is not None:
                 sc = sc.masked_fill(~keymask[:, None, None, :], float("-inf"))
+            if tri is not None:
+                sc = sc.masked_fill(~tri, float("-inf"))
             a = (sc.softmax(-1) @ v).transpose(1, 2).reshape(B, S, H)
             x = ln(x + lin(a, p("attention/output/dense")), p("attention/output/LayerNorm"))
             h = gelu(lin(x, p("intermediate/dense")))

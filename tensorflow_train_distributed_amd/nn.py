@@ -685,7 +685,7 @@ def global_avg_pool(x):
 # ------------------------------------------------------------------ attention
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, num_heads, rate, seqlen, site):
+    def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal):
         from .ops import transformer as T
         B, S, D = q.shape
         q2, k2, v2 = [t.reshape(B * S, D).to(torch.bfloat16).contiguous() for t in (q, k, v)]
@@ -696,26 +696,30 @@ class _Attention(torch.autograd.Function):
             rng = T.RngState(_Rng.seed, q.device)
             rng.t[1] = _Rng.offset
             _Rng.offset += 1
-        T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, seqlen=seqlen, p_drop=rate, rng=rng, site=site)
+        T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, seqlen=seqlen, p_drop=rate, rng=rng, site=site,
+                        causal=causal)
         ctx.save_for_backward(q2, k2, v2, o, lse, seqlen)
-        ctx.cfg = (B, S, D, num_heads, rate, rng, site, q.dtype)
+        ctx.cfg = (B, S, D, num_heads, rate, rng, site, q.dtype, causal)
         return o.reshape(B, S, D).to(q.dtype)
 
     @staticmethod
     def backward(ctx, do):
         from .ops import transformer as T
         q2, k2, v2, o, lse, seqlen = ctx.saved_tensors
-        B, S, D, nh, rate, rng, site, dt = ctx.cfg
+        B, S, D, nh, rate, rng, site, dt, causal = ctx.cfg
         d2 = do.reshape(B * S, D).to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2)
-        T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, seqlen=seqlen, p_drop=rate, rng=rng, site=site)
+        T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, seqlen=seqlen, p_drop=rate, rng=rng, site=site,
+                        causal=causal)
         return (dq.reshape(B, S, D).to(dt), dk.reshape(B, S, D).to(dt), dv.reshape(B, S, D).to(dt),
-                None, None, None, None)
+                None, None, None, None, None)
 
 
-def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0):
+def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0, causal: bool = False):
     """Multi-head scaled dot-product attention, token-major [B, S, num_heads*64] inputs,
-    keys >= seqlen[b] masked. GPU: the flash kernels (head_dim 64, S % 128 == 0)."""
+    keys >= seqlen[b] masked; causal=True also masks keys after the query (position s attends
+    positions <= s: a left-to-right language model). GPU: the flash kernels (head_dim 64,
+    S % 128 == 0); their causal form skips the key tiles above the diagonal."""
     B, S, D = q.shape
     hd = D // num_heads
     if _on_gpu(q, k, v):
@@ -725,7 +729,7 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
                 "(got head_dim %s, seq_len %d); pad the sequence (and mask it with seqlen) or use 64-wide heads"
                 % (D / num_heads, S))
         sl = seqlen.to(torch.int32).contiguous() if seqlen is not None else None
-        return _Attention.apply(q, k, v, num_heads, float(dropout_rate), sl, int(site))
+        return _Attention.apply(q, k, v, num_heads, float(dropout_rate), sl, int(site), bool(causal))
     qh = q.reshape(B, S, num_heads, hd).transpose(1, 2)
     kh = k.reshape(B, S, num_heads, hd).transpose(1, 2)
     vh = v.reshape(B, S, num_heads, hd).transpose(1, 2)
@@ -733,6 +737,9 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
     if seqlen is not None:
         m = torch.arange(S, device=q.device)[None, :] < seqlen[:, None].long()
         sc = sc.masked_fill(~m[:, None, None, :], float("-inf"))
+    if causal:
+        tri = torch.ones((S, S), dtype=torch.bool, device=q.device).tril()
+        sc = sc.masked_fill(~tri, float("-inf"))
     p = sc.softmax(-1)
     if dropout_rate > 0:
         p = F.dropout(p, dropout_rate, training=True)

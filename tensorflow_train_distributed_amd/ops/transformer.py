@@ -14,6 +14,8 @@ from ._lib import F, I, L, P
 _lib.register({
     "ttdk_attn_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, F, P, I, P],
     "ttdk_attn_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, P],
+    "ttdk_attn_fwd_causal": [P, L, P, L, P, L, P, L, P, P, I, I, I, F, P, I, I, P],
+    "ttdk_attn_bwd_causal": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, I, P],
     "ttdk_attn_set_fused_bwd": [I],
     "ttdk_ln_fwd": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
     "ttdk_ln_bwd_num_blocks": [I],
@@ -59,29 +61,35 @@ class RngState:
 
 
 # ------------------------------------------------------------------ attention
-def attention_fwd(q, k, v, out, lse, B, H, S, *, seqlen=None, p_drop=0.0, rng=None, site=0):
-    """q/k/v/out: 2-D bf16 views [B*S, >= H*64] (row stride = .stride(0)); lse fp32 [B*H, S]."""
-    _lib.call("ttdk_attn_fwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-              out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, float(p_drop),
-              _p(rng.t if rng is not None else None), int(site), _s())
+def attention_fwd(q, k, v, out, lse, B, H, S, *, seqlen=None, p_drop=0.0, rng=None, site=0, causal=False):
+    """q/k/v/out: 2-D bf16 views [B*S, >= H*64] (row stride = .stride(0)); lse fp32 [B*H, S].
+    causal: query s attends keys <= s only (combined with seqlen); the key tiles above the diagonal
+    are not streamed."""
+    _lib.call("ttdk_attn_fwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+              v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, float(p_drop),
+              _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
     return out, lse
 
 
 def set_fused_attention_bwd(on: bool):
     """Select the single-kernel attention backward (S in {128, 256, 512}; opt-in, measured slower
     at BERT-Large: attention.hip) or the split dQ / dK-dV kernels (default;
-    TTD_ATTN_FUSED_BWD=1 at start-up selects the fused one)."""
+    TTD_ATTN_FUSED_BWD=1 at start-up selects the fused one). A causal backward ignores the switch:
+    the fused kernel has no causal form, so attention_bwd(..., causal=True) always runs the split
+    kernels."""
     _lib.call("ttdk_attn_set_fused_bwd", int(bool(on)))
 
 
 def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, delta=None, seqlen=None, p_drop=0.0, rng=None,
-                  site=0):
+                  site=0, causal=False):
+    """Backward of attention_fwd with the same seqlen / p_drop / rng / site / causal."""
     if delta is None:
         delta = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
-    _lib.call("ttdk_attn_bwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-              o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(), delta.data_ptr(),
-              dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), _p(seqlen),
-              B, H, S, float(p_drop), _p(rng.t if rng is not None else None), int(site), _s())
+    _lib.call("ttdk_attn_bwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+              v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+              delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
+              dv.stride(0), _p(seqlen), B, H, S, float(p_drop), _p(rng.t if rng is not None else None), int(site),
+              int(bool(causal)), _s())
     return dq, dk, dv
 
 
