@@ -31,8 +31,9 @@ _LIBDIR = os.path.join(_PKG, "lib")
 _OBJDIR = os.path.join(_LIBDIR, "obj")
 
 RT_LIB = os.path.join(_LIBDIR, "libttd_rt.so")
-# kernel-side headers the host runtime also compiles (the collective engine's call plan)
-_RT_SHARED = [os.path.join(_CSRC, "kernels", "collective_plan.h")]
+# kernel-side headers the host runtime also compiles (the plans of the collective engine, the
+# direct xGMI all-reduce and the GEMM / convolution launchers)
+_RT_SHARED = [os.path.join(_CSRC, "kernels", h) for h in ("collective_plan.h", "ipc_plan.h", "gemm_plan.h")]
 HIP_LIB = os.path.join(_LIBDIR, "libttd_hip.so")
 
 HIP_ARCH = os.environ.get("TTD_HIP_ARCH", "gfx950")

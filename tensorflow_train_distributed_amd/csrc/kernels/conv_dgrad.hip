@@ -73,7 +73,7 @@ TTDK_EXPORT int ttdk_conv_dgrad(const bf16_t* dy, const bf16_t* wt, const TtdkCo
 // hipErrorNotSupported when the shape is not on the 256-row kernel (the caller keeps the pass).
 TTDK_EXPORT int ttdk_conv_dgrad_bnpro(const bf16_t* g_in, const bf16_t* wt, const TtdkConv* g, const bf16_t* y,
                                       const float* coef, bf16_t* dz, const TtdkEpilogue* epi, hipStream_t st) {
-  if (!(g->R == 1 && g->S == 1 && g->ph == 0 && g->pw == 0 && g->sh == 1 && g->sw == 1)) return hipErrorNotSupported;
+  if (!plan::conv_dgrad_bnpro_takes(*g)) return hipErrorNotSupported;
   EpiParams pe = to_epi(epi);
   if (pe.by && (pe.stat == nullptr || pe.mode != 0 || g->C % 8 || pe.ldo % 8 || pe.residual || pe.act))
     return hipErrorInvalidValue;
@@ -81,7 +81,7 @@ TTDK_EXPORT int ttdk_conv_dgrad_bnpro(const bf16_t* g_in, const bf16_t* wt, cons
   const int N = g->C, K = g->K;
   const int M = g->N * g->P * g->Q;
   const int bbn = big_bn(M, N, K);
-  if (!bbn || K % 64 || pe.mode != 0 || pe.remap) return hipErrorNotSupported;
+  if (pe.mode != 0 || pe.remap) return hipErrorNotSupported;
   pe.py = y;
   pe.pcoef = coef;
   pe.pdz = dz;
@@ -90,13 +90,6 @@ TTDK_EXPORT int ttdk_conv_dgrad_bnpro(const bf16_t* g_in, const bf16_t* wt, cons
   if (bbn == 256)
     return big::launch<256, big::OpDenseKBN<128, 2>, big::OpDenseK<128, 2>, 0, 0>(pa, pb, pe, M, N, K, 1, st);
   return big::launch<128, big::OpDenseKBN<128, 2>, big::OpDenseK<64, 2>, 0, 0>(pa, pb, pe, M, N, K, 1, st);
-}
-
-// Whether ttdk_conv_dgrad_bnpro runs this shape (its BN statistics rows are 256-row tiles).
-TTDK_EXPORT int ttdk_conv_dgrad_bnpro_ok(const TtdkConv* g) {
-  const int M = g->N * g->P * g->Q;
-  return g->R == 1 && g->S == 1 && g->ph == 0 && g->pw == 0 && g->sh == 1 && g->sw == 1 && g->K % 64 == 0 &&
-         big_bn(M, g->C, g->K) != 0;
 }
 
 // ---- strided dgrad by sub-pixel (phase) decomposition
@@ -126,19 +119,6 @@ __global__ __launch_bounds__(256) void subpixel_weights_kernel(const bf16_t* __r
   }
 }
 
-// Phase geometry along one axis: first tap, tap count, padding offset, phase extent.
-struct Phase {
-  int r0, T, off, n;
-};
-static Phase phase_of(int a, int s, int pad, int R, int H) {
-  Phase ph;
-  ph.r0 = (a + pad) % s;
-  ph.T = ph.r0 < R ? (R - ph.r0 + s - 1) / s : 0;
-  ph.off = (a + pad - ph.r0) / s;
-  ph.n = a < H ? (H - a + s - 1) / s : 0;
-  return ph;
-}
-
 // dx[N,H,W,C] of a strided conv (dilation 1, every phase has >= 1 tap) by phases. `ws`:
 // scratch for the phase sub-kernels, C*R*S*Kout bf16 (the size of wt); ws_ready != 0: ws
 // already holds the phase filters in this launcher's phase order (ttdk_wprep, once per step),
@@ -156,73 +136,47 @@ TTDK_EXPORT int ttdk_conv_dgrad_subpixel(const bf16_t* dy, const bf16_t* wt, con
   const size_t esz = pe.mode == 0 ? sizeof(bf16_t) : sizeof(float);
   bf16_t* wsp = ws;
   long long stat_row = 0;  // BN-backward statistics: each phase GEMM owns its own block of tile rows
-  for (int a = 0; a < s; ++a) {
-    const Phase pr = phase_of(a, s, g->ph, g->R, g->H);
-    for (int b = 0; b < s; ++b) {
-      const Phase pc = phase_of(b, s, g->pw, g->S, g->W);
-      if (pr.n == 0 || pc.n == 0) continue;
-      const int M = g->N * pr.n * pc.n, K = pr.T * pc.T * Kc;
-      const long long wn = static_cast<long long>(N) * K;
-      int grid = static_cast<int>(std::min<long long>((wn / 8 + 255) / 256, 4096));
-      if (!ws_ready)
-        hipLaunchKernelGGL(subpixel_weights_kernel, dim3(grid), dim3(256), 0, st, wt, wsp, N, g->R, g->S, Kc, s,
-                           pr.r0, pr.T, pc.r0, pc.T);
-      EpiParams e = pe;
-      e.remap = 1;
-      e.rP = pr.n;
-      e.rQ = pc.n;
-      e.rOH = g->H;
-      e.rOW = g->W;
-      e.rs = s;
-      const long long base = (static_cast<long long>(a) * g->W + b) * pe.ldo;  // phase origin (elements)
-      e.out = static_cast<char*>(pe.out) + base * esz;
-      hipError_t err;
-      const int bbn = big_bn(M, N, K);
-      if (pe.by) {
-        e.by = pe.by + base;
-        e.bmask = pe.bmask ? pe.bmask + base / 8 : nullptr;
-        e.stat = pe.stat + stat_row * 2 * N;
-        int pbm = 0, pbn = 0;
-        pick_tile(M, N, &pbm, &pbn);
-        stat_row += ceil_div(M, (bbn && Kc % 64 == 0) ? 256 : pbm);
-      }
-      if (bbn && Kc % 64 == 0) {
-        const big::ConvP pa{dy, g->P, g->Q, Kc, pr.n, pc.n, pr.T, pc.T, 1, 1, pr.off, pc.off, 1, 1, M};
-        const big::DenseP pb{wsp, K, N};
-        err = bbn == 256
-                  ? big::launch<256, big::OpConvK<128, 2, true, true>, big::OpDenseK<128, 2>>(pa, pb, e, M, N, K, 1, st)
-                  : big::launch<128, big::OpConvK<128, 2, true, true>, big::OpDenseK<64, 2>>(pa, pb, e, M, N, K, 1, st);
-      } else {
-        int bm = 0, bn = 0;
-        pick_tile(M, N, &bm, &bn);
-        GatherParams pa{dy, g->P, g->Q, Kc, pr.n, pc.n, pr.T, pc.T, 1, 1, pr.off, pc.off, 1, 1, M, K};
-        DenseParams pb{wsp, K, N, K};
-        err = dispatch<KConvDgrad, KDense>(&pa, &pb, e, M, N, K, 1, bm, bn, st);
-      }
-      if (err != hipSuccess) return err;
-      wsp += wn;
+  for (int i = 0; i < s * s; ++i) {  // the non-empty phases (a, b) in plan::phase_pair's order
+    plan::Phase pr, pc;
+    if (!plan::phase_pair(*g, i, &pr, &pc)) continue;
+    const int a = i / s, b = i % s;
+    const int M = g->N * pr.n * pc.n, K = pr.T * pc.T * Kc;
+    const long long wn = static_cast<long long>(N) * K;
+    int grid = static_cast<int>(std::min<long long>((wn / 8 + 255) / 256, 4096));
+    if (!ws_ready)
+      hipLaunchKernelGGL(subpixel_weights_kernel, dim3(grid), dim3(256), 0, st, wt, wsp, N, g->R, g->S, Kc, s,
+                         pr.r0, pr.T, pc.r0, pc.T);
+    EpiParams e = pe;
+    e.remap = 1;
+    e.rP = pr.n;
+    e.rQ = pc.n;
+    e.rOH = g->H;
+    e.rOW = g->W;
+    e.rs = s;
+    const long long base = (static_cast<long long>(a) * g->W + b) * pe.ldo;  // phase origin (elements)
+    e.out = static_cast<char*>(pe.out) + base * esz;
+    hipError_t err;
+    int bn = 0;
+    const int bm = plan::dgrad_tile(M, N, K, Kc, &bn);  // 256: the 256-row kernel, bn wide
+    if (pe.by) {
+      e.by = pe.by + base;
+      e.bmask = pe.bmask ? pe.bmask + base / 8 : nullptr;
+      e.stat = pe.stat + stat_row * 2 * N;
+      stat_row += ceil_div(M, bm);
     }
+    if (bm == 256) {
+      const big::ConvP pa{dy, g->P, g->Q, Kc, pr.n, pc.n, pr.T, pc.T, 1, 1, pr.off, pc.off, 1, 1, M};
+      const big::DenseP pb{wsp, K, N};
+      err = bn == 256
+                ? big::launch<256, big::OpConvK<128, 2, true, true>, big::OpDenseK<128, 2>>(pa, pb, e, M, N, K, 1, st)
+                : big::launch<128, big::OpConvK<128, 2, true, true>, big::OpDenseK<64, 2>>(pa, pb, e, M, N, K, 1, st);
+    } else {
+      GatherParams pa{dy, g->P, g->Q, Kc, pr.n, pc.n, pr.T, pc.T, 1, 1, pr.off, pc.off, 1, 1, M, K};
+      DenseParams pb{wsp, K, N, K};
+      err = dispatch<KConvDgrad, KDense>(&pa, &pb, e, M, N, K, 1, bm, bn, st);
+    }
+    if (err != hipSuccess) return err;
+    wsp += wn;
   }
   return hipGetLastError();
-}
-
-// Tile rows of the BN-backward partial-sum buffer ttdk_conv_dgrad_subpixel fills when its
-// epilogue carries statistics (sum over phases of each phase GEMM's row tiles).
-TTDK_EXPORT long long ttdk_conv_dgrad_subpixel_stat_rows(const TtdkConv* g) {
-  const int s = g->sh;
-  if (g->sw != s || s < 2) return -1;
-  const int N = g->C;
-  long long rows = 0;
-  for (int a = 0; a < s; ++a) {
-    const Phase pr = phase_of(a, s, g->ph, g->R, g->H);
-    for (int b = 0; b < s; ++b) {
-      const Phase pc = phase_of(b, s, g->pw, g->S, g->W);
-      if (pr.n == 0 || pc.n == 0) continue;
-      const int M = g->N * pr.n * pc.n, K = pr.T * pc.T * g->K;
-      int pbm = 0, pbn = 0;
-      pick_tile(M, N, &pbm, &pbn);
-      rows += ceil_div(M, (big_bn(M, N, K) && g->K % 64 == 0) ? 256 : pbm);
-    }
-  }
-  return rows;
 }

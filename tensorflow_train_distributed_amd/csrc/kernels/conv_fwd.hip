@@ -38,11 +38,11 @@ TTDK_EXPORT int ttdk_conv_fwd(const bf16_t* x, const bf16_t* w, const TtdkConv* 
 TTDK_EXPORT int ttdk_conv_fwd_bnpro(const bf16_t* y3, const bf16_t* w, const TtdkConv* g, const bf16_t* res,
                                     const float* coef, int proj, bf16_t* h_out, uint8_t* mask_out,
                                     const TtdkEpilogue* epi, hipStream_t st) {
-  if (!is_pointwise(g) || !res || !h_out || !mask_out) return hipErrorNotSupported;
+  if (!plan::conv_fwd_bnpro_takes(*g) || !res || !h_out || !mask_out) return hipErrorNotSupported;
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->P * g->Q, N = g->K, K = g->C;
   const int bbn = big_bn(M, N, K);
-  if (!bbn || K % 64 || pe.remap || pe.mode != 0) return hipErrorNotSupported;
+  if (pe.remap || pe.mode != 0) return hipErrorNotSupported;
   pe.py = res;
   pe.pcoef = coef;
   pe.pdz = h_out;

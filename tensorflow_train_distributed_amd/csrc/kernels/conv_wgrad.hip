@@ -6,27 +6,8 @@ extern "C" int ttdk_gemm4t_wgrad(const bf16_t* A, long long lda, const bf16_t* B
                                  hipStream_t st);
 extern "C" long long ttdk_gemm4t_ws(int M, int N, int K, int splits);
 
-// dw[K,R,S,C] (fp32) = sum over pixels of dy ⊗ im2col(x). `ws` is a split-K workspace of
-// splits*K*R*S*C floats (may be null when splits == 1, then dw is written directly).
-TTDK_EXPORT int ttdk_conv_wgrad(const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
-                                int splits, int beta, int bm, int bn, hipStream_t st) {
-  const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
-  if (g->C % 8 || g->K % 8) return hipErrorInvalidValue;
-  const int bbn = (bm == 0 || bm == 256) ? big_bn_wgrad(M, N, K) : 0;
-  if (bm == 0 || bn == 0 || bm == 256) pick_tile(M, N, &bm, &bn);
-  const int ktiles = ceil_div(K, BK);
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
-  if (splits > 1 && !ws) return hipErrorInvalidValue;
-  // unit-stride 1x1 convs with >= 256 output and input channels: the 4-wave transposed-read
-  // kernel (gemm4t.hip), split-K summed by the last split of each tile
-  if (bbn && is_pointwise(g) && M >= 256 && N >= 256 &&
-      (splits == 1 || ttdk_gemm4t_ws(M, N, K, splits) <= static_cast<long long>(splits) * M * N)) {
-    const int rc = ttdk_gemm4t_wgrad(dy, g->K, x, g->C, M, N, K, splits, ws, dw, beta, 1.f, nullptr, st);
-    if (rc != hipErrorInvalidValue) return rc;
-  }
+// fp32 epilogue of a split-K weight gradient: slabs into ws (splits > 1), else dw (+= with beta)
+static EpiParams wgrad_epi(int M, int N, int splits, float* dw, float* ws, int beta) {
   EpiParams pe{};
   pe.alpha = 1.f;
   pe.ldo = N;
@@ -39,6 +20,27 @@ TTDK_EXPORT int ttdk_conv_wgrad(const bf16_t* x, const bf16_t* dy, const TtdkCon
     pe.out = dw;
     pe.beta = beta;
   }
+  return pe;
+}
+
+// dw[K,R,S,C] (fp32) = sum over pixels of dy ⊗ im2col(x). `ws` is a split-K workspace of
+// splits*K*R*S*C floats (may be null when splits == 1, then dw is written directly).
+TTDK_EXPORT int ttdk_conv_wgrad(const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
+                                int splits, int beta, int bm, int bn, hipStream_t st) {
+  const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
+  if (g->C % 8 || g->K % 8) return hipErrorInvalidValue;
+  const int bbn = (bm == 0 || bm == 256) ? big_bn_wgrad(M, N, K) : 0;
+  if (bm == 0 || bn == 0 || bm == 256) pick_tile(M, N, &bm, &bn);
+  splits = plan::clamp_splits(ceil_div(K, BK), splits);
+  if (splits > 1 && !ws) return hipErrorInvalidValue;
+  // unit-stride 1x1 convs with >= 256 output and input channels: the 4-wave transposed-read
+  // kernel (gemm4t.hip), split-K summed by the last split of each tile
+  if (bbn && is_pointwise(g) && M >= 256 && N >= 256 &&
+      (splits == 1 || ttdk_gemm4t_ws(M, N, K, splits) <= static_cast<long long>(splits) * M * N)) {
+    const int rc = ttdk_gemm4t_wgrad(dy, g->K, x, g->C, M, N, K, splits, ws, dw, beta, 1.f, nullptr, st);
+    if (rc != hipErrorInvalidValue) return rc;
+  }
+  EpiParams pe = wgrad_epi(M, N, splits, dw, ws, beta);
   DenseParams pa{dy, g->K, M, K};
   hipError_t e;
   bool folded = false;
@@ -80,26 +82,11 @@ TTDK_EXPORT int ttdk_conv_wgrad_bn(const bf16_t* x, const bf16_t* g, const bf16_
                                    const TtdkConv* gm, float* dw, float* ws, int splits, int beta, int bm, int bn,
                                    hipStream_t st) {
   const int M = gm->K, N = gm->R * gm->S * gm->C, K = gm->N * gm->P * gm->Q;
-  if (gm->C % 8 || gm->K % 8 || is_pointwise(gm) || big_bn_wgrad(M, N, K)) return hipErrorInvalidValue;
+  if (!plan::conv_wgrad_bn_takes(*gm)) return hipErrorInvalidValue;
   if (bm == 0 || bn == 0 || bm == 256) pick_tile(M, N, &bm, &bn);
-  const int ktiles = ceil_div(K, BK);
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
+  splits = plan::clamp_splits(ceil_div(K, BK), splits);
   if (splits > 1 && !ws) return hipErrorInvalidValue;
-  EpiParams pe{};
-  pe.alpha = 1.f;
-  pe.ldo = N;
-  if (splits > 1) {
-    pe.mode = 1;
-    pe.out = ws;
-    pe.slab_stride = static_cast<long long>(M) * N;
-  } else {
-    pe.mode = 2;
-    pe.out = dw;
-    pe.beta = beta;
-  }
+  EpiParams pe = wgrad_epi(M, N, splits, dw, ws, beta);
   DenseBNParams pa{g, gm->K, M, K, y, coef};
   GatherParams pb{x, gm->H, gm->W, gm->C, gm->P, gm->Q, gm->R, gm->S, gm->sh, gm->sw, gm->ph, gm->pw, gm->dh, gm->dw, N, K};
   hipError_t e = dispatch<MNDenseBN, MNConvGather>(&pa, &pb, pe, M, N, K, splits, bm, bn, st);
@@ -118,30 +105,14 @@ TTDK_EXPORT int ttdk_conv_wgrad_fp8(const uint8_t* x8, const uint8_t* dy8, const
                                     int splits, int beta, const float* ascale_dy, const float* ascale_x,
                                     hipStream_t st) {
   const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
-  if (g->C % 16 || g->K % 16 || K % 128 || N < 256 || M < 16 || !ascale_dy || !ascale_x ||
-      static_cast<long long>(g->N) * g->H * g->W * g->C >= (1LL << 32) ||  // 32-bit im2col offsets
-      (reinterpret_cast<uintptr_t>(x8) & 15) || (reinterpret_cast<uintptr_t>(dy8) & 15))
+  if (!plan::conv_wgrad_fp8_takes(*g) || !ascale_dy || !ascale_x || (reinterpret_cast<uintptr_t>(x8) & 15) ||
+      (reinterpret_cast<uintptr_t>(dy8) & 15))
     return hipErrorInvalidValue;
-  const int ktiles = K / 128;
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
+  splits = plan::clamp_splits(K / 128, splits);
   if (splits > 1 && !ws) return hipErrorInvalidValue;
-  EpiParams pe{};
-  pe.alpha = 1.f;
+  EpiParams pe = wgrad_epi(M, N, splits, dw, ws, beta);
   pe.ascale0 = ascale_dy;
   pe.ascale1 = ascale_x;
-  pe.ldo = N;
-  if (splits > 1) {
-    pe.mode = 1;
-    pe.out = ws;
-    pe.slab_stride = static_cast<long long>(M) * N;
-  } else {
-    pe.mode = 2;
-    pe.out = dw;
-    pe.beta = beta;
-  }
   const big::DenseP pa{dy8, g->K, M};
   const big::ConvP pb = conv_params(x8, g->H, g->W, g->C, g->P, g->Q, g, N);
   // 256 x 128 tiles: with 256-wide tiles the i32x8 fragments and 128 accumulators held the whole

@@ -851,11 +851,10 @@ static int g4t_enabled() {
   return v;
 }
 
-// tile rows: 128 when the output has at most 128 rows (a 256-row tile would run half its MFMAs
-// on padding), else 256; the bias row sums (BERT) use the 256-row form. TTD_G4T_BM128=0: always 256.
+// tile rows (plan::g4t_bm); TTD_G4T_BM128=0: always 256
 static int g4t_bm(int M, bool rowsum) {
   static const int v = ttdk::getenv_int("TTD_G4T_BM128", 1);
-  return (v && !rowsum && M <= 128) ? 128 : 256;
+  return ttdk::plan::g4t_bm(M, rowsum, v != 0);
 }
 
 // floats of workspace ttdk_gemm4t_wgrad needs: split partial tiles + bias-gradient partials;
@@ -863,14 +862,8 @@ static int g4t_bm(int M, bool rowsum) {
 // except the leading dimensions / pointers, with lda = M and ldb = N)
 TTDK_EXPORT long long ttdk_gemm4t_ws(int M, int N, int K, int splits) {
   using namespace ttdk;
-  const long long lim = 1LL << 31;
-  if (!g4t_enabled() || K % 64 || K < 128 || M < 8 || N < 8 || M % 8 || N % 8 ||
-      static_cast<long long>(K) * M * 2 >= lim || static_cast<long long>(K) * N * 2 >= lim)
-    return -1;
-  const int ktiles = K / 64;
-  splits = std::max(1, std::min(splits, ktiles / 2));
-  const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
+  if (!g4t_enabled() || !plan::gemm4t_takes(M, N, K)) return -1;
+  splits = plan::clamp_splits_4t(K / 64, splits);
   // (sized for 256-row tiles: at least the 128-row form's need, and the bias row-sum form's)
   const int tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 256);
   return static_cast<long long>(splits) * tiles_m * tiles_n * 256 * 256 + static_cast<long long>(splits) * tiles_n * M;
@@ -883,16 +876,13 @@ TTDK_EXPORT int ttdk_gemm4t_wgrad(const bf16_t* A, long long lda, const bf16_t* 
                                   int splits, float* ws, float* out, int beta, float alpha, float* rowsum,
                                   hipStream_t st) {
   using namespace ttdk;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const long long lim = 1LL << 31;
-  if (!g4t_enabled() || K % 64 || K < 128 || M < 8 || N < 8 || M % 8 || N % 8 || lda % 8 || ldb % 8 || lda < M ||
-      ldb < N || !al16(A) || !al16(B) || !al16(out) || static_cast<long long>(K) * lda * 2 >= lim ||
-      static_cast<long long>(K) * ldb * 2 >= lim)
+  if (!g4t_enabled() || !plan::gemm4t_takes(M, N, K) || lda % 8 || ldb % 8 || lda < M || ldb < N || !al16(A) ||
+      !al16(B) || !al16(out) || static_cast<long long>(K) * lda * 2 >= lim || static_cast<long long>(K) * ldb * 2 >= lim)
     return hipErrorInvalidValue;
   const int ktiles = K / 64;
-  splits = std::max(1, std::min(splits, ktiles / 2));
+  splits = plan::clamp_splits_4t(ktiles, splits);
   const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
   const int bm = g4t_bm(M, rowsum != nullptr);
   const int tiles_m = ceil_div(M, bm), tiles_n = ceil_div(N, 256), tiles = tiles_m * tiles_n;
   int* ctr = nullptr;
@@ -924,44 +914,10 @@ void magic_div(unsigned d, unsigned* m, int* s) {
   *s = l > 0 ? l - 1 : 0;
   *m = static_cast<unsigned>(((static_cast<unsigned __int128>(1) << (32 + *s)) / d) + 1);
 }
-}  // namespace
 
-// floats of workspace ttdk_conv_wgrad4t needs (-1: the kernel does not take the conv)
-TTDK_EXPORT long long ttdk_conv_wgrad4t_ws(const TtdkConv* g, int splits) {
-  const int M = g->K, N = g->R * g->S * g->C;
-  const long long K = static_cast<long long>(g->N) * g->P * g->Q;
-  const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C * 2, yb = K * g->K * 2;
-  if (g->C % 8 || g->K % 8 || K % 64 || K < 128 || g->dh != 1 || g->dw != 1 || xb >= (1LL << 31) ||
-      yb >= (1LL << 31) || g->P * g->Q < 2 || g->Q < 2)
-    return -1;
-  return ttdk_gemm4t_ws(M, N, static_cast<int>(K), splits);
-}
-
-// Convolution weight gradient dw[K][R][S][C] (+)= sum over pixels of dy (x) im2col(x) on the 4-wave
-// transposed-read kernel: A = dy [pixels][K] (MN-major), B = x read through the im2col gather
-// (dense [pixels][C] for unit-stride 1x1 convs); split-K summed inside the launch (no fold pass).
-// ws: ttdk_conv_wgrad4t_ws floats. hipErrorInvalidValue: the kernel does not take the conv.
-TTDK_EXPORT int ttdk_conv_wgrad4t(const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
-                                  int splits, int beta, hipStream_t st) {
-  using namespace ttdk;
-  if (ttdk_conv_wgrad4t_ws(g, splits) < 0 || !g4t_enabled()) return hipErrorInvalidValue;
-  if (is_pointwise(g))
-    return ttdk_gemm4t_wgrad(dy, g->K, x, g->C, g->K, g->C, g->N * g->P * g->Q, splits, ws, dw, beta, 1.f, nullptr, st);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!al16(x) || !al16(dy) || !al16(dw) || !ws) return hipErrorInvalidValue;
-  const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
-  const int ktiles = K / 64;
-  splits = std::max(1, std::min(splits, ktiles / 2));
-  const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
-  const int bm = g4t_bm(M, false);
-  const int tiles_m = ceil_div(M, bm), tiles_n = ceil_div(N, 256), tiles = tiles_m * tiles_n;
-  int* ctr = nullptr;
-  if (splits > 1) {
-    ctr = big::tile_counters(st, tiles);
-    if (!ctr) return hipErrorInvalidValue;
-  }
-  g4t::Gather G{};
+// im2col gather of x for a weight gradient
+ttdk::g4t::Gather conv_gather(const TtdkConv* g) {
+  ttdk::g4t::Gather G{};
   G.H = g->H;
   G.W = g->W;
   G.C = g->C;
@@ -974,6 +930,39 @@ TTDK_EXPORT int ttdk_conv_wgrad4t(const bf16_t* x, const bf16_t* dy, const TtdkC
   G.pw = g->pw;
   magic_div(static_cast<unsigned>(G.PQ), &G.pq_m, &G.pq_s);
   magic_div(static_cast<unsigned>(G.Q), &G.q_m, &G.q_s);
+  return G;
+}
+}  // namespace
+
+// floats of workspace ttdk_conv_wgrad4t needs (-1: the kernel does not take the conv)
+TTDK_EXPORT long long ttdk_conv_wgrad4t_ws(const TtdkConv* g, int splits) {
+  if (!ttdk::plan::conv_wgrad4t_takes(*g)) return -1;
+  return ttdk_gemm4t_ws(g->K, g->R * g->S * g->C, g->N * g->P * g->Q, splits);
+}
+
+// Convolution weight gradient dw[K][R][S][C] (+)= sum over pixels of dy (x) im2col(x) on the 4-wave
+// transposed-read kernel: A = dy [pixels][K] (MN-major), B = x read through the im2col gather
+// (dense [pixels][C] for unit-stride 1x1 convs); split-K summed inside the launch (no fold pass).
+// ws: ttdk_conv_wgrad4t_ws floats. hipErrorInvalidValue: the kernel does not take the conv.
+TTDK_EXPORT int ttdk_conv_wgrad4t(const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
+                                  int splits, int beta, hipStream_t st) {
+  using namespace ttdk;
+  if (ttdk_conv_wgrad4t_ws(g, splits) < 0 || !g4t_enabled()) return hipErrorInvalidValue;
+  if (is_pointwise(g))
+    return ttdk_gemm4t_wgrad(dy, g->K, x, g->C, g->K, g->C, g->N * g->P * g->Q, splits, ws, dw, beta, 1.f, nullptr, st);
+  if (!al16(x) || !al16(dy) || !al16(dw) || !ws) return hipErrorInvalidValue;
+  const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
+  const int ktiles = K / 64;
+  splits = plan::clamp_splits_4t(ktiles, splits);
+  const int per = ceil_div(ktiles, splits);
+  const int bm = g4t_bm(M, false);
+  const int tiles_m = ceil_div(M, bm), tiles_n = ceil_div(N, 256), tiles = tiles_m * tiles_n;
+  int* ctr = nullptr;
+  if (splits > 1) {
+    ctr = big::tile_counters(st, tiles);
+    if (!ctr) return hipErrorInvalidValue;
+  }
+  const g4t::Gather G = conv_gather(g);
   const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C * 2;
   if (bm == 128)
     hipLaunchKernelGGL((g4t::gemm4t_kernel<false, true, 128>), dim3(tiles * splits), dim3(g4t::T), 0, st, dy,
@@ -991,16 +980,9 @@ TTDK_EXPORT int ttdk_conv_wgrad4t(const bf16_t* x, const bf16_t* dy, const TtdkC
 // multiple of 128 (whole K-tiles), operands under 2 GiB (the gather's out-of-range offset)
 TTDK_EXPORT long long ttdk_conv_wgrad4t8_ws(const TtdkConv* g, int splits) {
   using namespace ttdk;
+  if (!g4t_enabled() || !plan::conv_wgrad4t8_takes(*g)) return -1;
   const int M = g->K, N = g->R * g->S * g->C;
-  const long long K = static_cast<long long>(g->N) * g->P * g->Q;
-  const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C, yb = K * g->K;
-  if (!g4t_enabled() || g->C % 16 || g->K % 16 || M < 16 || N < 16 || K % 128 || K < 128 || g->dh != 1 ||
-      g->dw != 1 || xb >= (1LL << 31) || yb >= (1LL << 31) || (!is_pointwise(g) && (g->P * g->Q < 2 || g->Q < 2)))
-    return -1;
-  const int ktiles = static_cast<int>(K / 128);
-  splits = std::max(1, std::min(splits, ktiles / 2));
-  const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
+  splits = plan::clamp_splits_4t(g->N * g->P * g->Q / 128, splits);
   return static_cast<long long>(splits) * ceil_div(M, 256) * ceil_div(N, 256) * 256 * 256;
 }
 
@@ -1012,14 +994,12 @@ TTDK_EXPORT long long ttdk_conv_wgrad4t8_ws(const TtdkConv* g, int splits) {
 TTDK_EXPORT int ttdk_conv_wgrad4t8(const uint8_t* x8, const uint8_t* dy8, const TtdkConv* g, float* dw, float* ws,
                                    int splits, int beta, const float* sa, const float* sx, hipStream_t st) {
   using namespace ttdk;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (ttdk_conv_wgrad4t8_ws(g, splits) < 0 || !sa || !sx || !al16(x8) || !al16(dy8) || !al16(dw))
     return hipErrorInvalidValue;
   const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
   const int ktiles = K / 128;
-  splits = std::max(1, std::min(splits, ktiles / 2));
+  splits = plan::clamp_splits_4t(ktiles, splits);
   const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
   const int tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 256), tiles = tiles_m * tiles_n;
   int* ctr = nullptr;
   if (splits > 1) {
@@ -1034,18 +1014,7 @@ TTDK_EXPORT int ttdk_conv_wgrad4t8(const uint8_t* x8, const uint8_t* dy8, const 
                        G, 0LL);
     return hipGetLastError();
   }
-  G.H = g->H;
-  G.W = g->W;
-  G.C = g->C;
-  G.Q = g->Q;
-  G.PQ = g->P * g->Q;
-  G.S = g->S;
-  G.sh = g->sh;
-  G.sw = g->sw;
-  G.ph = g->ph;
-  G.pw = g->pw;
-  magic_div(static_cast<unsigned>(G.PQ), &G.pq_m, &G.pq_s);
-  magic_div(static_cast<unsigned>(G.Q), &G.q_m, &G.q_s);
+  G = conv_gather(g);
   const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C;
   hipLaunchKernelGGL((g4t::gemm4t8_kernel<true>), grid, dim3(g4t::T), 0, st, dy8, static_cast<long long>(g->K), x8, 0LL,
                      M, N, K, tiles_m, tiles_n, splits, per, ws, dw, beta, sa, sx, ctr, G, xb);

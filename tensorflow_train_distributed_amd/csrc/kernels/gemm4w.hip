@@ -1243,11 +1243,7 @@ TTDK_EXPORT int ttdk_conv_fwd4w(const bf16_t* x, const bf16_t* w, const TtdkConv
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->P * g->Q, N = g->K, K = g->R * g->S * g->C;
   const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C * 2;
-  const long long shift = (static_cast<long long>(g->ph) * g->W + g->pw) * g->C * 2;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (g->C % 64 || K < 128 || N % 8 || g->dh != 1 || g->dw != 1 || g->R * g->S > 32 || M < 1 || !al16(x) ||
-      !al16(w) || !al16(pe.out) || xb + shift >= (1LL << 31) || (static_cast<long long>(N) + 256) * K * 2 >= (1LL << 32) ||
-      static_cast<long long>(M) * N * 2 >= (1LL << 40) || pe.ldo != N || pe.bias || pe.residual ||
+  if (!plan::conv_fwd4w_takes(*g) || !al16(x) || !al16(w) || !al16(pe.out) || pe.ldo != N || pe.bias || pe.residual ||
       pe.act != kActNone || pe.aux || pe.beta || pe.remap || pe.mode != 0 || pe.by || pe.bH || pe.alpha != 1.f ||
       pe.ascale0 || pe.ascale1)
     return hipErrorInvalidValue;
@@ -1287,11 +1283,7 @@ TTDK_EXPORT int ttdk_conv_dgrad4w(const bf16_t* dy, const bf16_t* wt, const Ttdk
   const int M = g->N * g->H * g->W, N = g->C, K = g->R * g->S * g->K;
   const long long yb = static_cast<long long>(g->N) * g->P * g->Q * g->K * 2;
   const int pho = g->R - 1 - g->ph, pwo = g->S - 1 - g->pw;
-  const long long shift = (static_cast<long long>(pho) * g->Q + pwo) * g->K * 2;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (g->sh != 1 || g->sw != 1 || g->dh != 1 || g->dw != 1 || g->K % 64 || K < 128 || N % 8 || g->R * g->S > 32 ||
-      pho < 0 || pwo < 0 || M < 1 || !al16(dy) || !al16(wt) || !al16(pe.out) || yb + shift >= (1LL << 31) ||
-      (static_cast<long long>(N) + 256) * K * 2 >= (1LL << 32) || pe.ldo != N || pe.bias || pe.residual ||
+  if (!plan::conv_dgrad4w_takes(*g) || !al16(dy) || !al16(wt) || !al16(pe.out) || pe.ldo != N || pe.bias || pe.residual ||
       pe.act != kActNone || pe.aux || pe.beta || pe.remap || pe.mode != 0 || pe.bH || pe.by2 || pe.stat2 ||
       pe.alpha != 1.f || pe.ascale0 || pe.ascale1 || (pe.by != nullptr) != (pe.stat != nullptr) ||
       (pe.by && !al16(pe.by)))
@@ -1314,7 +1306,6 @@ TTDK_EXPORT int ttdk_gemm4w_bf16(const bf16_t* A, long long lda, const bf16_t* B
                                  const TtdkEpilogue* epi, hipStream_t st) {
   using namespace ttdk;
   EpiParams pe = to_epi(epi);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const long long lim = 1LL << 32;
   if (K < 64 || K % 64 || N % 8 || lda % 8 || ldb % 8 || pe.ldo % 8 || !al16(A) || !al16(B) || !al16(pe.out) ||
       (static_cast<long long>(M) + 256) * lda * 2 >= lim || (static_cast<long long>(N) + 256) * ldb * 2 >= lim ||
@@ -1393,12 +1384,7 @@ TTDK_EXPORT int ttdk_conv_fwd4k8(const uint8_t* x8, const uint8_t* w8, const Ttd
   using namespace ttdk;
   const int M = g->N * g->P * g->Q, N = g->K, K = g->R * g->S * g->C;
   const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C;
-  const long long shift = (static_cast<long long>(g->ph) * g->W + g->pw) * g->C;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (g->C % 128 || N % 8 || N < 8 || M < 1 || g->dh != 1 || g->dw != 1 || g->R * g->S > 32 || !sa || !sw ||
-      !al16(x8) || !al16(w8) || !al16(out) || xb + shift >= (1LL << 31) ||
-      (static_cast<long long>(N) + 256) * K >= (1LL << 32))
-    return hipErrorInvalidValue;
+  if (!plan::conv_fwd4k8_takes(*g) || !sa || !sw || !al16(x8) || !al16(w8) || !al16(out)) return hipErrorInvalidValue;
   g4::K8Args P{};
   P.A = x8;
   P.lda = g->C;
@@ -1417,7 +1403,6 @@ TTDK_EXPORT int ttdk_conv_fwd4k8(const uint8_t* x8, const uint8_t* w8, const Ttd
   P.group = g4_group();
   const dim3 grid(P.tiles_m * P.tiles_n);
   if (is_pointwise(g)) {
-    if (static_cast<long long>(M) * g->C >= (1LL << 32)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((g4::gemm4k8_kernel<0, false>), grid, dim3(g4::T), 0, st, P, g4::ConvA{});
     return hipGetLastError();
   }
@@ -1440,11 +1425,7 @@ TTDK_EXPORT int ttdk_conv_dgrad4k8(const uint8_t* dy8, const uint8_t* wt8, const
   const int M = g->N * g->H * g->W, N = g->C, K = g->R * g->S * g->K;
   const long long yb = static_cast<long long>(g->N) * g->P * g->Q * g->K;
   const int pho = g->R - 1 - g->ph, pwo = g->S - 1 - g->pw;
-  const long long shift = (static_cast<long long>(pho) * g->Q + pwo) * g->K;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (g->sh != 1 || g->sw != 1 || g->dh != 1 || g->dw != 1 || g->K % 128 || N % 8 || N < 8 || g->R * g->S > 32 ||
-      pho < 0 || pwo < 0 || M < 1 || !sa || !sw || !al16(dy8) || !al16(wt8) || !al16(out) ||
-      yb + shift >= (1LL << 31) || (static_cast<long long>(N) + 256) * K >= (1LL << 32) ||
+  if (!plan::conv_dgrad4k8_takes(*g) || !sa || !sw || !al16(dy8) || !al16(wt8) || !al16(out) ||
       (by != nullptr) != (stat != nullptr) || (by != nullptr) != (bmask != nullptr) || (by && (reinterpret_cast<uintptr_t>(by) & 7)) ||
       (beta && !by))
     return hipErrorInvalidValue;

@@ -27,6 +27,7 @@
 //  * Optional fused epilogue: bias, ReLU/GELU, residual add, accumulate-into-output,
 //    strided output-row remap (stride-2 1x1 dgrad), per-tile BatchNorm partial sums.
 #include "common.h"
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -42,6 +43,10 @@ int& fold_flag();
 
 namespace ttdk {
 namespace {
+
+using plan::big_bn;
+using plan::big_bn_wgrad;
+using plan::pick_tile;
 
 constexpr int BK = 64;
 constexpr int NTHR = 256;
@@ -1040,6 +1045,8 @@ hipError_t splitk_reduce(const float* ws_c, int splits, long long n, float* out,
 }
 
 // integer environment switch (A/B runs)
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 inline int getenv_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
@@ -2485,14 +2492,11 @@ hipError_t launch(const typename OA::Params& pa, const typename OB::Params& pb, 
   // kernel far beyond rounding (profiles/r3_tail_split_check.json: gradient cosine 0.81), so it is gone.)
   const int cus = device_cus();
   const int tiles = tm * tn;
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
+  splits = plan::clamp_splits(ktiles, splits);
   const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
   if constexpr (F8 == 0 && PP == 1 && OA::THREADS == THR && BN == 256) {
     // elementwise-only epilogue on more than one round of tiles: persistent kernel, the next
     // tile's operand DMA in flight under this tile's register epilogue
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     int ek = -1;
     if (pe.act == kActNone && !pe.residual) ek = 0;
     else if (pe.act == kActGelu && !pe.residual) ek = kEkGelu;
@@ -2557,10 +2561,8 @@ inline hipError_t dense_rowsum(const bf16_t* A, long long lda, const bf16_t* B, 
   DenseP pa{A, lda, M}, pb{B, ldb, N};
   const int tm = ceil_div(M, BM), tn = ceil_div(N, 256);
   const int ktiles = K / 64;
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
+  splits = plan::clamp_splits(ktiles, splits);
   const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
   hipLaunchKernelGGL((gemm256_kernel<256, OpDenseMN<128>, OpDenseMN<128>, 0, 1, 1>), dim3(tm * tn, splits), dim3(THR), 0,
                      st, pa, pb, pe, M, N, K, tm, tn, per, 0);
   return hipGetLastError();
@@ -2586,10 +2588,8 @@ hipError_t launch(const typename LA::Params& pa, const typename LB::Params& pb, 
                   int K, int splits, hipStream_t st) {
   const int tm = ceil_div(M, BM), tn = ceil_div(N, BN);
   const int ktiles = ceil_div(K, BK);
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
+  splits = plan::clamp_splits(ktiles, splits);
   const int per = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, per);
   dim3 grid(tm * tn, splits);
   hipLaunchKernelGGL((gemm_kernel<BM, BN, LA, LB>), grid, dim3(NTHR), 0, st, pa, pb, pe, M, N, K, tm, tn, per);
   return hipGetLastError();
@@ -2605,26 +2605,7 @@ hipError_t launch_batched(const typename LA::Params& pa, const typename LB::Para
   return hipGetLastError();
 }
 
-// Tile choice: prefer 128x128; shrink a dimension when it is small.
-// Tile width of the 256-row LDS-DMA kernel for an M x N x K GEMM, or 0 when the 4-wave
-// kernel is the better fit (small tiles / small GEMMs). Mirrored by ops/gemm.py big_bn().
-inline int big_bn(int M, int N, int K) {
-  if (M < 256 || N < 128 || K % 64 || N % 8 || static_cast<long long>(M) * N < (1LL << 20)) return 0;
-  return N >= 256 ? 256 : 128;
-}
-inline bool big_fits(int M, int N, int K) { return big_bn(M, N, K) != 0; }
-// Weight gradients have a long K (pixels) and split-K fills the machine, so only the tile
-// shape (not M*N) decides.
-inline int big_bn_wgrad(int M, int N, int K) {
-  if (M < 256 || N < 128 || K % 64 || N % 8) return 0;
-  return N >= 256 ? 256 : 128;
-}
-
-inline void pick_tile(int M, int N, int* bm, int* bn) {
-  *bm = (M <= 64) ? 64 : 128;
-  *bn = (N <= 64) ? 64 : 128;
-}
-
+// (tile choice: plan::big_bn / big_bn_wgrad / pick_tile, gemm_plan.h)
 template <template <int> class LA_T, template <int> class LB_T>
 hipError_t dispatch(const void* pa_raw, const void* pb_raw, const EpiParams& pe, int M, int N, int K, int splits,
                     int bm, int bn, hipStream_t st) {
@@ -2721,16 +2702,7 @@ inline EpiParams to_epi(const TtdkEpilogue* e) {
   return p;
 }
 
-struct TtdkConv {
-  int N, H, W, C;   // input NHWC
-  int K, R, S;      // filters [K][R][S][C]
-  int P, Q;         // output spatial
-  int sh, sw, ph, pw, dh, dw;
-};
-
-inline bool is_pointwise(const TtdkConv* g) {
-  return g->R == 1 && g->S == 1 && g->sh == 1 && g->sw == 1 && g->ph == 0 && g->pw == 0;
-}
+inline bool is_pointwise(const TtdkConv* g) { return plan::is_pointwise(*g); }
 
 // y[N,P,Q,K] = conv(x[N,H,W,C], w[K,R,S,C]).
 inline big::ConvP conv_params(const void* src, int Hs, int Ws, int Cs, int P, int Q, const TtdkConv* g, int rows) {

@@ -14,10 +14,9 @@ TTDK_EXPORT int ttdk_gemm_bf16(const bf16_t* A, long long lda, int a_kmajor, con
                                int b_kmajor, int M, int N, int K, int splits, int bm, int bn,
                                const TtdkEpilogue* epi, hipStream_t st) {
   EpiParams pe = to_epi(epi);
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // 16-B vector operand loads need the contiguous dim and the leading dim to be multiples
   // of 8 elements and 16-B aligned bases; otherwise both operands use the masked scalar path.
-  const bool vec = al(A) && al(B) && lda % 8 == 0 && ldb % 8 == 0 && (a_kmajor ? K % 8 == 0 : M % 8 == 0) &&
+  const bool vec = al16(A) && al16(B) && lda % 8 == 0 && ldb % 8 == 0 && (a_kmajor ? K % 8 == 0 : M % 8 == 0) &&
                    (b_kmajor ? K % 8 == 0 : N % 8 == 0);
   DenseParams pa{A, lda, M, K};
   DenseParams pb{B, ldb, N, K};
@@ -62,9 +61,8 @@ TTDK_EXPORT int ttdk_gemm_bf16(const bf16_t* A, long long lda, int a_kmajor, con
 TTDK_EXPORT int ttdk_gemm_bf16_batched(const bf16_t* A, long long lda, long long sa, int a_kmajor, const bf16_t* B,
                                        long long ldb, long long sb, int b_kmajor, void* out, long long ldo,
                                        long long so, int out_fp32, int M, int N, int K, int batch, hipStream_t st) {
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch > 65535) return hipErrorInvalidValue;
-  const bool vec = al(A) && al(B) && lda % 8 == 0 && ldb % 8 == 0 && sa % 8 == 0 && sb % 8 == 0 &&
+  const bool vec = al16(A) && al16(B) && lda % 8 == 0 && ldb % 8 == 0 && sa % 8 == 0 && sb % 8 == 0 &&
                    (a_kmajor ? K % 8 == 0 : M % 8 == 0) && (b_kmajor ? K % 8 == 0 : N % 8 == 0);
   TtdkEpilogue te{};
   te.mode = out_fp32 ? 2 : 0;
@@ -113,8 +111,7 @@ TTDK_EXPORT int ttdk_gemm_bf16_splitk(const bf16_t* A, long long lda, int a_kmaj
   te.slab_stride = static_cast<long long>(M) * N;
   te.alpha = alpha;
   EpiParams pe = to_epi(&te);
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = al(A) && al(B) && lda % 8 == 0 && ldb % 8 == 0 && (a_kmajor ? K % 8 == 0 : M % 8 == 0) &&
+  const bool vec = al16(A) && al16(B) && lda % 8 == 0 && ldb % 8 == 0 && (a_kmajor ? K % 8 == 0 : M % 8 == 0) &&
                    (b_kmajor ? K % 8 == 0 : N % 8 == 0);
   const int bbn = big_bn(M, N, K);
   const int ktiles = K / 64;
@@ -155,9 +152,7 @@ TTDK_EXPORT long long ttdk_gemm_wgrad_bias_ws(int M, int N, int K, int splits) {
   const long long w4 = ttdk_gemm4t_ws(M, N, K, splits);
   if (big_bn(M, N, K) != 256 || M % 8 || N % 8 || K % 64) return w4;
   const int ktiles = K / 64;
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  splits = ceil_div(ktiles, ceil_div(ktiles, splits));
+  splits = plan::clamp_splits(ktiles, splits);
   return std::max(w4, static_cast<long long>(splits) * M * N + static_cast<long long>(splits) * ceil_div(N, 256) * M);
 }
 
@@ -168,13 +163,10 @@ TTDK_EXPORT int ttdk_gemm_wgrad_bias(const bf16_t* A, long long lda, const bf16_
     const int rc = ttdk_gemm4t_wgrad(A, lda, B, ldb, M, N, K, splits, ws, out, beta, alpha, rowsum, st);
     if (rc != hipErrorInvalidValue) return rc;
   }
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!al(A) || !al(B) || lda % 8 || ldb % 8 || M % 8 || N % 8 || K % 64 || big_bn(M, N, K) != 256 || !rowsum)
+  if (!al16(A) || !al16(B) || lda % 8 || ldb % 8 || M % 8 || N % 8 || K % 64 || big_bn(M, N, K) != 256 || !rowsum)
     return hipErrorInvalidValue;
   const int ktiles = K / 64;
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  splits = ceil_div(ktiles, ceil_div(ktiles, splits));
+  splits = plan::clamp_splits(ktiles, splits);
   if (ceil_div(ktiles, splits) < 16) return hipErrorInvalidValue;  // the ping-pong schedule's K-tile floor
   TtdkEpilogue te{};
   te.mode = 1;

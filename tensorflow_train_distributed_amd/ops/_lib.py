@@ -60,11 +60,9 @@ _SIGS = {
     "ttdk_conv_dgrad4w": [P, P, G, E, P],
     "ttdk_conv_dgrad": [P, P, G, I, I, E, P],
     "ttdk_conv_dgrad_bnpro": [P, P, G, P, P, P, E, P],
-    "ttdk_conv_dgrad_bnpro_ok": [G],
     "ttdk_set_inkernel_fold": [I],
     "ttdk_conv_fwd_bnpro": [P, P, G, P, P, I, P, P, E, P],
     "ttdk_conv_dgrad_subpixel": [P, P, G, P, I, E, P],
-    "ttdk_conv_dgrad_subpixel_stat_rows": [G],
     "ttdk_conv_wgrad": [P, P, G, P, P, I, I, I, I, P],
     "ttdk_conv_wgrad4t": [P, P, G, P, P, I, I, P],
     "ttdk_conv_wgrad4t_ws": [G, I],
@@ -149,7 +147,7 @@ def register(sigs: dict):
     _SIGS.update(sigs)
 
 
-_RESTYPE = {"ttdk_conv_dgrad_subpixel_stat_rows": c_longlong, "ttdk_colsum_ws_floats": c_longlong,
+_RESTYPE = {"ttdk_colsum_ws_floats": c_longlong,
             "ttdk_gemm_wgrad_bias_ws": c_longlong, "ttdk_gemm4t_ws": c_longlong,
             "ttdk_conv_wgrad4t_ws": c_longlong, "ttdk_conv_wgrad4t8_ws": c_longlong}
 

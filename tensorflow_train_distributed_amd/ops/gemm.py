@@ -10,7 +10,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, _plan
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH, ACT_DGELU = 0, 1, 2, 3, 4
 
@@ -59,31 +59,20 @@ def _epi(out, *, mode=0, ldo=None, bias=None, residual=None, act=0, beta=0, stat
     return e
 
 
-def big_bn(M, N, K):
-    """Mirror of the C++ big_bn(): tile width (256 / 128) of the 256-row LDS-DMA kernel for an
-    M x N x K GEMM, or 0 when the 4-wave kernel is used."""
-    if M < 256 or N < 128 or K % 64 or N % 8 or M * N < (1 << 20):
-        return 0
-    return 256 if N >= 256 else 128
+# big_bn(M, N, K): tile width (256 / 128) of the 256-row LDS-DMA kernel for an M x N x K GEMM, or 0
+# when the 4-wave kernel is used; big_bn_wgrad: for conv weight gradients (long K, split-K: only
+# the tile shape decides)
+big_bn, big_bn_wgrad = _plan.big_bn, _plan.big_bn_wgrad
 
 
 def big_fits(M, N, K):
     return big_bn(M, N, K) != 0
 
 
-def big_bn_wgrad(M, N, K):
-    """Mirror of the C++ big_bn_wgrad() (conv weight gradients: long K, split-K)."""
-    if M < 256 or N < 128 or K % 64 or N % 8:
-        return 0
-    return 256 if N >= 256 else 128
-
-
 def effective_splits(K, splits, bk=64):
-    """Mirror of the kernel launcher's split-K clamping (every split gets >= 1 K-tile)."""
-    kt = -(-K // bk)
-    splits = max(1, min(splits, kt))
-    per = -(-kt // splits)
-    return -(-kt // per)
+    """The split-K factor the launchers run for a request of `splits` (every split gets >= 1
+    K-tile of bk, none is empty)."""
+    return _plan.clamp_splits(-(-K // bk), splits)
 
 
 def _check(t, dtype, name):
@@ -239,9 +228,7 @@ def wgrad_bias_ok(M, N, K, splits) -> bool:
     if int(_lib.query("ttdk_gemm_wgrad_bias_ws", int(M), int(N), int(K), int(splits))) < 0:
         return False
     kt = K // 64
-    s = max(1, min(int(splits), kt))
-    per = -(-kt // s)
-    return per >= 16
+    return -(-kt // _plan.clamp_splits(kt, int(splits))) >= 16
 
 
 def gemm_wgrad_bias(dy, x, out, bias_out, splits=1, beta=0, alpha=1.0):
@@ -412,8 +399,7 @@ def gemm_wgrad_splits(M, N, K, target_blocks=1024, min_ktiles=8, big_wgs=None):
     if bbn:
         tiles = -(-M // 256) * -(-N // bbn)
         return max(1, min((K // 64) // 32, -(-(big_wgs or BIG_WGRAD_WGS) // tiles)))
-    bm = 64 if M <= 64 else 128
-    bn = 64 if N <= 64 else 128
+    bm, bn = _plan.pick_tile(M, N)
     tiles = -(-M // bm) * -(-N // bn)
     ktiles = -(-K // 64)
     return max(1, min(ktiles // min_ktiles, -(-target_blocks // tiles)))
@@ -589,11 +575,7 @@ def conv_fwd4w_pays(x_shape, w_shape, stride=(1, 1), padding=(0, 0)) -> bool:
 
 def conv_fwd4w_ok(x_shape, w_shape, stride=(1, 1), padding=(0, 0)) -> bool:
     """Whether conv_fwd4w takes this conv: C % 64 == 0, K % 8 == 0, R*S*C >= 128, operands in range."""
-    g = conv_geom(tuple(x_shape), tuple(w_shape), stride, padding)
-    xb = g.N * g.H * g.W * g.C * 2
-    shift = (g.ph * g.W + g.pw) * g.C * 2
-    return (g.C % 64 == 0 and g.K % 8 == 0 and g.R * g.S * g.C >= 128 and g.R * g.S <= 32
-            and g.dh == 1 and g.dw == 1 and xb + shift < (1 << 31))
+    return _plan.takes("conv_fwd4w", conv_geom(tuple(x_shape), tuple(w_shape), stride, padding))
 
 
 def conv_fwd4w(x, w, stride=(1, 1), padding=(0, 0), *, stat=True, out=None):
@@ -625,10 +607,8 @@ _DGRAD4W = int(_os.environ.get("TTD_DGRAD4W", "1"))
 def conv_dgrad4w_pays(x_shape, wt_shape, stride=(1, 1), padding=(0, 0)) -> bool:
     """conv_dgrad takes the 4-wave kernel for this unit-stride, non-pointwise data gradient."""
     C, R, S, K = wt_shape
-    if _DGRAD4W <= 0 or tuple(stride) != (1, 1) or R * S == 1 or K % 64 or C % 8:
-        return False
-    g = conv_geom(tuple(x_shape), (K, R, S, C), stride, padding)
-    if g.ph > R - 1 or g.pw > S - 1 or g.N * g.P * g.Q * K * 2 + ((R - 1 - g.ph) * g.Q + S - 1 - g.pw) * K * 2 >= (1 << 31):
+    if _DGRAD4W <= 0 or R * S == 1 or not _plan.takes("conv_dgrad4w", conv_geom(tuple(x_shape), (K, R, S, C), stride,
+                                                                                padding)):
         return False
     KK = R * S * K
     return _DGRAD4W >= 2 or (C >= 256 and KK >= 1024 and KK * C >= 512 * 1024)
@@ -636,10 +616,7 @@ def conv_dgrad4w_pays(x_shape, wt_shape, stride=(1, 1), padding=(0, 0)) -> bool:
 
 def conv_fwd_bnpro_ok(x_shape, w_shape):
     """Whether conv_fwd_bnpro runs: a 1x1 unit-stride conv on the 256-row kernel."""
-    N, H, W, C = x_shape
-    K = w_shape[0]
-    return (tuple(w_shape[1:3]) == (1, 1) and C % 64 == 0 and C == w_shape[3]
-            and big_bn(N * H * W, K, C) != 0)
+    return x_shape[3] == w_shape[3] and _plan.takes("conv_fwd_bnpro", conv_geom(x_shape, w_shape, (1, 1), (0, 0)))
 
 
 def conv_fwd_bnpro(y3, w, coef, res, h_out, mask_out, *, proj=False):
@@ -674,21 +651,19 @@ def conv_fwd_bnpro(y3, w, coef, res, h_out, mask_out, *, proj=False):
 _SUBPIXEL = _os.environ.get("TTD_SUBPIXEL_DGRAD", "1") != "0"
 
 
-def _phases(s, pad, R, H):
-    """(taps, extent) of each sub-pixel phase along one axis (mirror of gemm_conv.hip phase_of)."""
-    out = []
-    for a in range(s):
-        r0 = (a + pad) % s
-        T = (R - r0 + s - 1) // s if r0 < R else 0
-        n = (H - a + s - 1) // s if a < H else 0
-        if n:
-            out.append((T, n))
-    return out
+subpixel_phases = _plan.subpixel_phases
 
 
-def _pick_tile(M, N):
-    """Mirror of the C++ pick_tile() (4-wave kernel tile)."""
-    return (64 if M <= 64 else 128), (64 if N <= 64 else 128)
+def _subpixel_call(dy, wt, g, ws, e):
+    """Strided dgrad as s*s unit-stride phase GEMMs (skips the zero taps of the direct gather);
+    one log line per phase GEMM, in ttdk_conv_dgrad_subpixel's launch order."""
+    if _LOG is not None:
+        for pr, pc in subpixel_phases(g):
+            _log("dgrad_%dx%d_s%d_phase%dx%d" % (g.R, g.S, g.sh, pr.T, pc.T), g.N * pr.n * pc.n, g.C, pr.T * pc.T * g.K)
+    ready = ws is not None
+    ws = torch.empty_like(wt) if ws is None else ws
+    _lib.call("ttdk_conv_dgrad_subpixel", dy.data_ptr(), wt.data_ptr(), ctypes.byref(g), ws.data_ptr(), int(ready),
+              ctypes.byref(e), _lib.stream())
 
 
 def _subpixel_ok(g, R, S, stride, padding):
@@ -708,7 +683,7 @@ def dgrad_stat_rows(x_shape, wt_shape, stride=(1, 1), padding=(0, 0)):
         g = conv_geom(tuple(x_shape), (K, R, S, C), stride, padding)
         if not _subpixel_ok(g, R, S, stride, padding):
             return None
-        return int(_lib.fn("ttdk_conv_dgrad_subpixel_stat_rows")(ctypes.byref(g)))
+        return _plan.subpixel_stat_rows(g)
     return dgrad_stat_tile(x_shape, wt_shape)[2]
 
 
@@ -718,28 +693,20 @@ DGRAD_STAT_4W_K = int(_os.environ.get("TTD_DGRAD_STAT_4W_K", "0"))
 
 
 def dgrad_stat_tile(x_shape, wt_shape, stride=(1, 1), padding=(0, 0)):
-    """(bm, bn, rows) of a unit-stride data-gradient launch with the BN-statistics epilogue
-    (mirror of ttdk_conv_dgrad's tile choice when `stat` is set)."""
+    """(bm, bn, rows) of a unit-stride data-gradient launch with the BN-statistics epilogue: the
+    tile conv_dgrad asks ttdk_conv_dgrad for and the rows of its partial-sum buffer. (Pointwise
+    gradients up to DGRAD_STAT_4W_K: the 4-wave kernel, two workgroups per CU; A/B:
+    tools/dgrad_epi_ab.py.)"""
     C, R, S, K = wt_shape
-    N, H, W, _ = x_shape
     if tuple(stride) != (1, 1):
         return None
-    pointwise = R == 1 and S == 1 and tuple(padding) == (0, 0)
-    M = N * H * W
-    Kg = R * S * K
-    bbn = big_bn(M, C, Kg)
-    if pointwise and Kg <= DGRAD_STAT_4W_K:
-        bbn = 0  # 4-wave kernel, two workgroups per CU (A/B: tools/dgrad_epi_ab.py)
-    if bbn and (pointwise or K % 64 == 0):
-        return 256, bbn, -(-M // 256)
-    bm, bn = _pick_tile(M, C)
-    return bm, bn, -(-M // bm)
+    return _plan.dgrad_stat(conv_geom(tuple(x_shape), (K, R, S, C), stride, padding), DGRAD_STAT_4W_K)
 
 
 def _bnpro_call(dy, wt, g, bn_pro, e):
     y, coef, dz = bn_pro
     C, R, S, K = wt.shape
-    if not _lib.fn("ttdk_conv_dgrad_bnpro_ok")(ctypes.byref(g)):
+    if not _plan.takes("conv_dgrad_bnpro", g):
         raise ValueError("conv_dgrad: the BN-backward operand prologue needs a 1x1 unit-stride dgrad on the 256-row "
                          "kernel")
     _check(y, torch.bfloat16, "bn_pro y")
@@ -756,8 +723,7 @@ def dgrad_bnpro_ok(x_shape, wt_shape, stride=(1, 1), padding=(0, 0)):
     """Whether conv_dgrad(bn_pro=...) runs: a 1x1 unit-stride data gradient on the 256-row
     kernel (K % 64 == 0)."""
     C, R, S, K = wt_shape
-    g = conv_geom(tuple(x_shape), (K, R, S, C), stride, padding)
-    return bool(_lib.fn("ttdk_conv_dgrad_bnpro_ok")(ctypes.byref(g)))
+    return _plan.takes("conv_dgrad_bnpro", conv_geom(tuple(x_shape), (K, R, S, C), stride, padding))
 
 
 def conv_dgrad(dy, wt, x_shape, stride=(1, 1), padding=(0, 0), *, out=None, beta=0, residual=None,
@@ -809,15 +775,7 @@ def conv_dgrad(dy, wt, x_shape, stride=(1, 1), padding=(0, 0), *, out=None, beta
         e = _epi(out, ldo=C, beta=beta, stat=partial, by=y, bmask=mask, by2=bn_stat2, stat2=partial2,
                  beta_s2=beta_s2 if beta else None)
         if tuple(stride) != (1, 1):
-            if _LOG is not None:
-                for pa in _phases(g.sh, g.ph, R, g.H):
-                    for pb in _phases(g.sw, g.pw, S, g.W):
-                        _log("dgrad_%dx%d_s%d_phase%dx%d" % (R, S, g.sh, pa[0], pb[0]), g.N * pa[1] * pb[1], C,
-                             pa[0] * pb[0] * K)
-            ready = ws is not None
-            ws = torch.empty_like(wt) if ws is None else ws
-            _lib.call("ttdk_conv_dgrad_subpixel", dy.data_ptr(), wt.data_ptr(), ctypes.byref(g), ws.data_ptr(),
-                      int(ready), ctypes.byref(e), _lib.stream())
+            _subpixel_call(dy, wt, g, ws, e)
         elif bn_pro is not None:
             _bnpro_call(dy, wt, g, bn_pro, e)
         elif (not beta and partial2 is None and residual is None
@@ -840,16 +798,7 @@ def conv_dgrad(dy, wt, x_shape, stride=(1, 1), padding=(0, 0), *, out=None, beta
         _bnpro_call(dy, wt, g, bn_pro, e)
         return out
     if _subpixel_ok(g, R, S, stride, padding) and residual is None and tile == (0, 0):
-        # strided dgrad as s*s unit-stride phase GEMMs (skips the zero taps of the direct gather)
-        if _LOG is not None:  # one GEMM per phase, in ttdk_conv_dgrad_subpixel's launch order
-            for pa in _phases(g.sh, g.ph, R, g.H):
-                for pb in _phases(g.sw, g.pw, S, g.W):
-                    _log("dgrad_%dx%d_s%d_phase%dx%d" % (R, S, g.sh, pa[0], pb[0]), g.N * pa[1] * pb[1], C,
-                         pa[0] * pb[0] * K)
-        ready = ws is not None
-        ws = torch.empty_like(wt) if ws is None else ws
-        _lib.call("ttdk_conv_dgrad_subpixel", dy.data_ptr(), wt.data_ptr(), ctypes.byref(g), ws.data_ptr(),
-                  int(ready), ctypes.byref(e), _lib.stream())
+        _subpixel_call(dy, wt, g, ws, e)
         return out
     _log("dgrad_%dx%d_s%d" % (R, S, stride[0]), g.N * (g.P * g.Q if strided_pw else g.H * g.W), C, R * S * K)
     _lib.call("ttdk_conv_dgrad", dy.data_ptr(), wt.data_ptr(), ctypes.byref(g), tile[0], tile[1], ctypes.byref(e),
@@ -878,8 +827,7 @@ def wgrad_splits(g, target_blocks=None, min_ktiles=8):
         # element per split (write + reduce read)
         tiles = -(-M // 256) * -(-N // bbn)
         return max(1, min((K // 64) // 32, -(-BIG_WGRAD_WGS // tiles)))
-    bm = 64 if M <= 64 else 128
-    bn = 64 if N <= 64 else 128
+    bm, bn = _plan.pick_tile(M, N)
     tiles = -(-M // bm) * -(-N // bn)
     ktiles = -(-K // 64)
     if (g.R > 1 or g.S > 1) and tiles <= 16 and _WGRAD_GATHER_X3:
@@ -917,9 +865,12 @@ _WGRAD4T_SMALL = _os.environ.get("TTD_WGRAD4T_SMALL", "none")
 _WGRAD4T_MINM = int(_os.environ.get("TTD_WGRAD4T_MINM", "128"))
 
 
+_G4T_BM128 = _os.environ.get("TTD_G4T_BM128", "1") != "0"  # gemm4t.hip reads the same switch
+
+
 def wgrad4t_rows(M: int) -> int:
-    """Output rows per tile of the 4-wave weight-gradient kernel (mirror of gemm4t.hip g4t_bm)."""
-    return 128 if (M <= 128 and _os.environ.get("TTD_G4T_BM128", "1") != "0") else 256
+    """Output rows per tile of the 4-wave weight-gradient kernel (gemm4t.hip)."""
+    return _plan.g4t_bm(M, False, _G4T_BM128)
 
 
 def conv_wgrad4t_splits(g, target_blocks=None, min_ktiles=None):
@@ -1002,10 +953,7 @@ def conv_wgrad(x, dy, w_shape, stride=(1, 1), padding=(0, 0), *, out=None, beta=
 def conv_wgrad_fp8_ok(x_shape, w_shape, stride=(1, 1), padding=(0, 0)):
     """Whether conv_wgrad_fp8 takes this weight gradient: C and K multiples of 16, the pixel
     count a multiple of 128, R*S*C >= 256, the fp8 input under 4 GiB."""
-    g = conv_geom(tuple(x_shape), tuple(w_shape), stride, padding)
-    pixels = g.N * g.P * g.Q
-    return (g.C % 16 == 0 and g.K % 16 == 0 and pixels % 128 == 0 and g.R * g.S * g.C >= 256
-            and g.N * g.H * g.W * g.C < (1 << 32))
+    return _plan.takes("conv_wgrad_fp8", conv_geom(tuple(x_shape), tuple(w_shape), stride, padding))
 
 
 def conv_wgrad_fp8(x8, dy8, w_shape, stride=(1, 1), padding=(0, 0), *, ascale, out=None, beta=0, splits=None):
@@ -1053,10 +1001,7 @@ def conv_wgrad_fp8(x8, dy8, w_shape, stride=(1, 1), padding=(0, 0), *, ascale, o
 
 def conv_wgrad_bn_fusable(x_shape, w_shape, stride=(1, 1), padding=(0, 0)):
     """Whether conv_wgrad_bn runs for this conv (non-pointwise, 4-wave im2col-gather kernel)."""
-    g = conv_geom(x_shape, w_shape, stride, padding)
-    M, N, K = g.K, g.R * g.S * g.C, g.N * g.P * g.Q
-    pointwise = g.R == 1 and g.S == 1 and g.sh == 1 and g.sw == 1 and g.ph == 0 and g.pw == 0
-    return not pointwise and g.C % 8 == 0 and g.K % 8 == 0 and not big_bn_wgrad(M, N, K)
+    return _plan.takes("conv_wgrad_bn", conv_geom(x_shape, w_shape, stride, padding))
 
 
 def conv_wgrad_bn(x, g_out, y, coef, w_shape, stride=(1, 1), padding=(0, 0), *, out=None, beta=0, splits=None):
@@ -1194,14 +1139,8 @@ _DGRAD4K8_BETA = _os.environ.get("TTD_DGRAD4K8_BETA", "0") != "0"
 
 
 def conv_fwd4k8_ok(x_shape, w_shape, stride=(1, 1), padding=(0, 0)) -> bool:
-    """Whether conv_fwd4k8 takes this conv (mirror of ttdk_conv_fwd4k8's admission)."""
-    if not _CONV4K8:
-        return False
-    g = conv_geom(tuple(x_shape), tuple(w_shape), stride, padding)
-    M, N, K = g.N * g.P * g.Q, g.K, g.R * g.S * g.C
-    xb = g.N * g.H * g.W * g.C + (g.ph * g.W + g.pw) * g.C
-    return (g.C % 128 == 0 and N % 8 == 0 and N >= 8 and M >= 1 and g.R * g.S <= 32 and xb < (1 << 31)
-            and (N + 256) * K < (1 << 32) and M * g.C < (1 << 32))
+    """Whether conv_fwd4k8 takes this conv (and is enabled: TTD_CONV4K8)."""
+    return _CONV4K8 and _plan.takes("conv_fwd4k8", conv_geom(tuple(x_shape), tuple(w_shape), stride, padding))
 
 
 def conv_fwd4k8_pays(x_shape, w_shape, stride=(1, 1), padding=(0, 0)) -> bool:
@@ -1238,6 +1177,18 @@ def conv_dgrad_fp8_ok(x_shape, wt_shape, stride=(1, 1), padding=(0, 0)):
     return tuple(stride) == (1, 1) and K % 128 == 0 and C % 8 == 0
 
 
+def conv_dgrad_fp8_path(x_shape, wt_shape, stride=(1, 1), padding=(0, 0), *, beta, stat, beta_s2) -> str:
+    """Which kernel conv_dgrad_fp8 runs: "4-wave" (gemm4w.hip gemm4k8_kernel) on the long-reduction
+    shapes of the TTD_DGRAD4K8* policy that its launcher admits, else "8-wave". stat / beta_s2:
+    whether the call has a bn_stat / a beta_s2 argument."""
+    C, R, S, K = wt_shape
+    policy = (_DGRAD4K8 and (not beta or (_DGRAD4K8_BETA and stat and not beta_s2))
+              and R * S * K >= _DGRAD4K8_MINK and C >= _DGRAD4K8_MINC)
+    if policy and _plan.takes("conv_dgrad4k8", conv_geom(tuple(x_shape), (K, R, S, C), stride, padding)):
+        return "4-wave"
+    return "8-wave"
+
+
 def conv_dgrad_fp8(dy8, wt8, x_shape, stride=(1, 1), padding=(0, 0), *, ascale, out=None, beta=0, bn_stat=None,
                    beta_s2=None):
     """fp8 data gradient: dy8 [N,P,Q,K] OCP e5m2 (uint8), wt8 [C,R,S,K] e4m3 (uint8), unit
@@ -1253,8 +1204,8 @@ def conv_dgrad_fp8(dy8, wt8, x_shape, stride=(1, 1), padding=(0, 0), *, ascale, 
     if out is None:
         out = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dy8.device)
     M = g.N * g.H * g.W
-    if (_DGRAD4K8 and (not beta or (_DGRAD4K8_BETA and bn_stat is not None and beta_s2 is None))
-            and R * S * K >= _DGRAD4K8_MINK and C >= _DGRAD4K8_MINC):
+    if conv_dgrad_fp8_path(x_shape, wt8.shape, stride, padding, beta=beta, stat=bn_stat is not None,
+                           beta_s2=beta_s2 is not None) == "4-wave":
         # the 4-wave fp8 kernel (gemm4w.hip gemm4k8_kernel, reversed-tap gather of dy8) on the
         # long-reduction shapes; its statistics come per 128 rows
         T = 2 * (-(-M // 256))

@@ -6,7 +6,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _plan
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 
@@ -300,19 +300,6 @@ def krsc_to_crsk(w, out=None):
     return out
 
 
-def subpixel_phases(s, pad, R, H):
-    """(first tap, tap count) of each non-empty sub-pixel phase along one axis of a stride-s
-    data gradient, in ttdk_conv_dgrad_subpixel's order (mirror of conv_dgrad.hip phase_of)."""
-    out = []
-    for a in range(s):
-        r0 = (a + pad) % s
-        T = (R - r0 + s - 1) // s if r0 < R else 0
-        n = (H - a + s - 1) // s if a < H else 0
-        if n:
-            out.append((r0, T))
-    return out
-
-
 class TransposeBatch:
     """bf16 [A][C] -> [C][A] for a fixed list of (src, dst) 2-D tensor pairs in ONE launch
     (ttdk_transpose128_batch_bf16; A and C multiples of 128, 16-B aligned, contiguous rows).
@@ -399,9 +386,9 @@ class WeightPrep:
             return
         s, ph, pw, H, W = sub
         start = self._dst_n
-        for r0, Tr in subpixel_phases(s, ph, R, H):
-            for s0, Ts in subpixel_phases(s, pw, S, W):
-                self._entry(offset, shape, s, r0, Tr, s0, Ts)
+        g = _lib.ConvGeom(N=1, H=H, W=W, C=C, K=K, R=R, S=S, sh=s, sw=s, ph=ph, pw=pw, dh=1, dw=1)
+        for pr, pc in _plan.subpixel_phases(g):  # ttdk_conv_dgrad_subpixel's launch order
+            self._entry(offset, shape, s, pr.r0, pr.T, pc.r0, pc.T)
         self._views[name] = ("phases", start, self._dst_n - start)
 
     def build(self):

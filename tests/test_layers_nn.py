@@ -226,7 +226,9 @@ def test_weight_prep_table_layout_cpu():
         if R == 3:
             ph = wp.phases(n + "/phases")
             assert ph.numel() == C * R * S * Kc  # the phases partition the 9 taps
-            want = [(T1, T2) for (T1, _) in G._phases(2, 1, 3, 28) for (T2, _) in G._phases(2, 1, 3, 28)]
+            want = [(pr.T, pc.T) for pr, pc in
+                    G.subpixel_phases(G.conv_geom((1, 28, 28, C), (Kc, 3, 3, C), (2, 2), (1, 1)))]
+            assert want == [(1, 1), (1, 2), (2, 1), (2, 2)]  # 3 taps, stride 2, pad 1: phase 0 one tap, phase 1 two
             got = [(int(r["Tr"]), int(r["Ts"])) for r in rows if r["s"] == 2 and r["K"] == Kc and r["C"] == C]
             assert got == want
     ends = sorted((v[1], v[1] + (int(np.prod(v[2])) if v[0] == "crsk" else v[2])) for v in wp._views.values())
