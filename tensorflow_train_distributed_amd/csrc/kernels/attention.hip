@@ -17,6 +17,20 @@
 // bwd_kv 577 us against 782 us — with the rotated block order of causal_block(); in natural or
 // heavy-first order the causal kernels gain 6 % at most (profiles/attn_causal_bench.txt).
 //
+//
+// Cross-attention (ttdk_attn_fwd_cross / ttdk_attn_bwd_cross): the query length S and the key
+// length Sk are separate (a decoder's attention over an encoder's output). Every kernel owns
+// 128 rows of one kind and streams 64-row tiles of the other, so only the index arithmetic
+// tells them apart:
+//   query rows (Q, O, dO, dQ)  token base b*S,  lse / delta row bh*S + q, S/128 blocks in fwd and
+//                              bwd_q, S/64 streamed tiles in bwd_kv;
+//   key rows (K, V, dK, dV)    token base b*Sk, len = min(seqlen[b], Sk) — seqlen is the memory's
+//                              length, queries are never masked — Sk/128 blocks in bwd_kv.
+// The dropout hash takes row id bh*S + q and a pair term of the key index alone, so with Sk == S
+// it is the self-attention hash and a longer memory extends a shorter one's mask. fwd and bwd_q
+// launch B*H*S/128 workgroups, bwd_kv B*H*Sk/128. The causal instantiations and the fused
+// backward are for Sk == S only.
+//
 // Kernels (4 waves / workgroup, XCD-aware block order so the Q-blocks of one head share an
 // L2):
 //   fwd     : 128 query rows per workgroup (32 per wave); K/V tiles of 64 keys double-buffered
@@ -65,7 +79,8 @@ struct AttnParams {
   float* lse;          // [B*H][S] log2 domain
   float* delta;        // [B*H][S]: written by bwd_q, read by bwd_kv
   const int* seqlen;   // [B] or null
-  int B, H, S;
+  int B, H, S;         // S: query rows per batch (Q, O, dO, dQ, lse, delta)
+  int Sk;              // key rows per batch (K, V, dK, dV); == S for self-attention
   float scale_log2;    // log2(e) / sqrt(D)
   float scale;         // 1 / sqrt(D)
   uint32_t drop_thr;
@@ -162,8 +177,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int q0 = qblk * QBLK + wave * 32;
-  const int len = P.seqlen ? min(P.seqlen[b], P.S) : P.S;
-  const long long tok0 = static_cast<long long>(b) * P.S;
+  const int len = P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;
+  const long long tok0 = static_cast<long long>(b) * P.S;    // query rows: Q, O, dO, dQ
+  const long long tokk = static_cast<long long>(b) * P.Sk;   // key rows: K, V, dK, dV
 
   bf16x8_t qf[2][2];
 #pragma unroll
@@ -173,8 +189,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
       qf[qb][ks] = ldg_frag(P.q + (tok0 + q0 + qb * 16 + i16) * P.ldq + h * D + ks * 32 + g * 8);
 
   TileLoader lk, lv;
-  lk.init(P.k + tok0 * P.ldk + h * D, P.ldk, tid);
-  lv.init(P.v + tok0 * P.ldv + h * D, P.ldv, tid);
+  lk.init(P.k + tokk * P.ldk + h * D, P.ldk, tid);
+  lv.init(P.v + tokk * P.ldv + h * D, P.ldv, tid);
 
   float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
   f32x4_t o[2][4];
@@ -357,7 +373,7 @@ template <bool DROP, int MODE = 0, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   constexpr int BUF = 2 * TILE_BYTES + 2 * KT * 4;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
-  const int kblocks = P.S / QBLK;
+  const int kblocks = P.Sk / QBLK;
   const int t = tile::xcd_remap(blockIdx.x, gridDim.x);
   const int bh = t / kblocks;
   int kblk = t - bh * kblocks;
@@ -366,8 +382,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int k0 = kblk * QBLK + wave * 32;
-  const int len = P.seqlen ? min(P.seqlen[b], P.S) : P.S;
-  const long long tok0 = static_cast<long long>(b) * P.S;
+  const int len = P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;
+  const long long tok0 = static_cast<long long>(b) * P.S;    // query rows: Q, O, dO, dQ
+  const long long tokk = static_cast<long long>(b) * P.Sk;   // key rows: K, V, dK, dV
   long long stamp[6] = {};
   if constexpr ((MODE & 8) != 0) {
     stamp[0] = __builtin_amdgcn_s_memtime();
@@ -387,7 +404,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const long long row = tok0 + k0 + kb * 16 + i16;
+        const long long row = tokk + k0 + kb * 16 + i16;
         kf[kb][ks] = ldg_frag(P.k + row * P.ldk + h * D + ks * 32 + g * 8);
         vf[kb][ks] = ldg_frag(P.v + row * P.ldv + h * D + ks * 32 + g * 8);
       }
@@ -402,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     const float st_mul = tid >= KT && DROP ? 1.f / P.drop_scale : 1.f;
     float stv = 0.f;
     const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
-    const int ntiles = P.S / KT;  // even: S is a multiple of QBLK = 2 * KT
+    const int ntiles = P.S / KT;  // query tiles; even: S is a multiple of QBLK = 2 * KT
 
     auto load = [&](int qt) {
       lq.load(qt * KT, P.S);
@@ -581,7 +598,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   // >= len get zeros (their accumulators saw unmasked probabilities)
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
-    const long long row = tok0 + k0 + kb * 16 + i16;
+    const long long row = tokk + k0 + kb * 16 + i16;
     bf16_t* pk = P.out + row * P.ld_out + h * D + 4 * g;
     bf16_t* pv = P.out2 + row * P.ld_out2 + h * D + 4 * g;
     const bool valid = k0 + kb * 16 + i16 < len;
@@ -623,8 +640,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int q0 = qblk * QBLK + wave * 32;
-  const int len = P.seqlen ? min(P.seqlen[b], P.S) : P.S;
-  const long long tok0 = static_cast<long long>(b) * P.S;
+  const int len = P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;
+  const long long tok0 = static_cast<long long>(b) * P.S;    // query rows: Q, O, dO, dQ
+  const long long tokk = static_cast<long long>(b) * P.Sk;   // key rows: K, V, dK, dV
 
   bf16x8_t qf[2][2], df[2][2];
   float lse2[2], del[2];
@@ -662,8 +680,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     for (int db = 0; db < 4; ++db) dq[qb][db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   TileLoader lk, lv;
-  lk.init(P.k + tok0 * P.ldk + h * D, P.ldk, tid);
-  lv.init(P.v + tok0 * P.ldv + h * D, P.ldv, tid);
+  lk.init(P.k + tokk * P.ldk + h * D, P.ldk, tid);
+  lv.init(P.v + tokk * P.ldv + h * D, P.ldv, tid);
   const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
   int ntiles = (len + KT - 1) / KT;
   if constexpr (CAUSAL) ntiles = min(ntiles, 2 * qblk + 2);
@@ -1036,11 +1054,13 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_fused_kernel(AttnParams P
   }
 }
 
-AttnParams make_params(int B, int H, int S, const int* seqlen, float p_drop, const long long* rng, uint32_t site) {
+AttnParams make_params(int B, int H, int S, int Sk, const int* seqlen, float p_drop, const long long* rng,
+                       uint32_t site) {
   AttnParams P{};
   P.B = B;
   P.H = H;
   P.S = S;
+  P.Sk = Sk;
   P.seqlen = seqlen;
   P.scale = 0.125f;  // 1/sqrt(64)
   P.scale_log2 = 0.125f * 1.4426950408889634f;
@@ -1074,17 +1094,21 @@ using namespace ttdk;
 // Shapes: S % 128 == 0, head_dim 64, every ld % 8 == 0 and bases 16-B aligned (checked).
 // Returns hipErrorInvalidValue on violation (the Python wrapper raises).
 // causal != 0: query q attends keys k <= q (and k < seqlen[b]).
-TTDK_EXPORT int ttdk_attn_fwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                     long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
-                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
-                                     hipStream_t st) {
-  if (S % QBLK || (ldq | ldk | ldv | ldo) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
-      (p_drop > 0.f && !rng))
+//
+// Cross-attention: q / o have Sq rows per batch, k / v have Sk rows (the memory); lse is
+// [B*H][Sq]; seqlen[b] is the memory's valid length (keys >= it masked; queries are never
+// masked). Sq % 128 == 0 and Sk % 128 == 0; causal needs Sq == Sk.
+TTDK_EXPORT int ttdk_attn_fwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                    long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
+                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
+                                    int causal, hipStream_t st) {
+  if (Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) || (ldq | ldk | ldv | ldo) & 7 ||
+      !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (p_drop > 0.f && !rng))
     return hipErrorInvalidValue;
-  AttnParams P = make_params(B, H, S, seqlen, p_drop, rng, site);
+  AttnParams P = make_params(B, H, Sq, Sk, seqlen, p_drop, rng, site);
   P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
   P.out = o; P.ld_out = ldo; P.lse = lse;
-  dim3 grid(B * H * (S / QBLK)), block(256);
+  dim3 grid(B * H * (Sq / QBLK)), block(256);
   if (causal) {
     P.order = causal_order();
     if (p_drop > 0.f) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, st, P);
@@ -1095,6 +1119,13 @@ TTDK_EXPORT int ttdk_attn_fwd_causal(const bf16_t* q, long long ldq, const bf16_
     hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, st, P);
   }
   return hipGetLastError();
+}
+
+TTDK_EXPORT int ttdk_attn_fwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                     long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
+                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
+                                     hipStream_t st) {
+  return ttdk_attn_fwd_cross(q, ldq, k, ldk, v, ldv, o, ldo, lse, seqlen, B, H, S, S, p_drop, rng, site, causal, st);
 }
 
 TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
@@ -1125,22 +1156,26 @@ TTDK_EXPORT int ttdk_attn_set_fused_bwd(int on) {
 }
 
 // dq/dk/dv may alias one fused [tokens, 3*H*64] buffer (different column offsets).
-// causal != 0: the backward of ttdk_attn_fwd_causal(..., causal); split kernels only.
-TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                     long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
-                                     long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
-                                     bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
-                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
-                                     hipStream_t st) {
-  if (S % QBLK || (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7 || !aligned16(q) || !aligned16(k) ||
-      !aligned16(v) || !aligned16(o) || !aligned16(dout) || (p_drop > 0.f && !rng))
+// causal != 0: the backward of ttdk_attn_fwd_cross(..., causal); split kernels only.
+// Sq != Sk (cross-attention): split kernels only as well — bwd_q over B*H*Sq/128 workgroups, then
+// bwd_kv over B*H*Sk/128; dq has Sq rows per batch, dk / dv have Sk, lse / delta are [B*H][Sq].
+TTDK_EXPORT int ttdk_attn_bwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                    long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
+                                    long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
+                                    bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
+                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
+                                    int causal, hipStream_t st) {
+  if (Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) ||
+      (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) ||
+      !aligned16(o) || !aligned16(dout) || (p_drop > 0.f && !rng))
     return hipErrorInvalidValue;
-  AttnParams P = make_params(B, H, S, seqlen, p_drop, rng, site);
+  const int S = Sq;
+  AttnParams P = make_params(B, H, Sq, Sk, seqlen, p_drop, rng, site);
   P.q = q; P.k = k; P.v = v; P.o = o; P.dout = dout;
   P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo; P.lddo = lddo;
   P.lse = const_cast<float*>(lse);
   P.delta = delta;
-  if (!causal && attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
+  if (!causal && Sq == Sk && attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
     // one workgroup per (batch, head): dQ, dK, dV in one pass (attn_bwd_fused_kernel)
     P.out = dq; P.ld_out = lddq; P.out2 = dk; P.ld_out2 = lddk; P.out3 = dv; P.ld_out3 = lddv;
     const dim3 g1(B * H);
@@ -1158,7 +1193,8 @@ TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_
     }
     return hipGetLastError();
   }
-  dim3 grid(B * H * (S / QBLK)), block(256);
+  // bwd_q owns query blocks, bwd_kv key blocks: two grid sizes when Sq != Sk
+  dim3 grid(B * H * (Sq / QBLK)), grid_kv(B * H * (Sk / QBLK)), block(256);
   // dQ first: it computes delta (rowsum dO . O) on the way and stores it for dK / dV
   P.out = dq; P.ld_out = lddq; P.out2 = nullptr;
   if (causal) {
@@ -1179,18 +1215,28 @@ TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_
   }();
   if (p_drop > 0.f) {
     switch (kv_diag) {
-      case 1: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 1>), grid, block, 0, st, P); break;
-      case 2: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 2>), grid, block, 0, st, P); break;
-      case 6: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 6>), grid, block, 0, st, P); break;
-      case 7: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 7>), grid, block, 0, st, P); break;
-      case 8: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 8>), grid, block, 0, st, P); break;
-      case 15: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 15>), grid, block, 0, st, P); break;
-      default: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0>), grid, block, 0, st, P);
+      case 1: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 1>), grid_kv, block, 0, st, P); break;
+      case 2: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 2>), grid_kv, block, 0, st, P); break;
+      case 6: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 6>), grid_kv, block, 0, st, P); break;
+      case 7: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 7>), grid_kv, block, 0, st, P); break;
+      case 8: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 8>), grid_kv, block, 0, st, P); break;
+      case 15: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 15>), grid_kv, block, 0, st, P); break;
+      default: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0>), grid_kv, block, 0, st, P);
     }
   } else {
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid, block, 0, st, P);
+    hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid_kv, block, 0, st, P);
   }
   return hipGetLastError();
+}
+
+TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                     long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
+                                     long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
+                                     bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
+                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
+                                     hipStream_t st) {
+  return ttdk_attn_bwd_cross(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv,
+                             seqlen, B, H, S, S, p_drop, rng, site, causal, st);
 }
 
 TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,

@@ -22,6 +22,7 @@ import torch
 
 from .. import initializers as I
 from .. import nn as N
+from ..utils.errors import InvalidArgumentError
 
 _name_uid: Dict[str, int] = collections.defaultdict(int)
 _depth = [0]  # nesting depth of Layer calls (the outermost call owns the model)
@@ -316,10 +317,16 @@ class Embedding(Layer):
 
 
 class MultiHeadAttention(Layer):
-    """Self-attention with fused QKV projection (head size 64 on the GPU flash kernels).
-    call(x, seqlen=None, training=True, use_causal_mask=False): keys >= seqlen[b] are masked;
-    use_causal_mask=True (Keras' name) lets position s attend positions <= s only, the
-    decoder-only / left-to-right form."""
+    """Attention with fused QKV projection (head size 64 on the GPU flash kernels).
+    call(x, value=None, seqlen=None, training=True, use_causal_mask=False): keys >= seqlen[b] are
+    masked; use_causal_mask=True (Keras' name) lets position s attend positions <= s only, the
+    decoder-only / left-to-right form.
+    value=None is self-attention: one fused QKV GEMM on x. value [B, Sk, D] (x's width; Keras'
+    MultiHeadAttention(query, value)) is cross-attention, an encoder-decoder's attention over the
+    encoder's output: the queries come from x through the first `inner` columns of qkv/kernel and
+    qkv/bias, keys and values from `value` through the other 2*inner — the same variables, so
+    names, counts and checkpoints do not depend on how the layer is called. seqlen is then the
+    memory's valid length; a causal mask needs Sk == S."""
     _default_name = "multi_head_attention"
 
     def __init__(self, num_heads, key_dim=64, dropout=0.0, name=None):
@@ -336,10 +343,20 @@ class MultiHeadAttention(Layer):
         self.add_weight("output/bias", (D,), "zeros", attr="out_bias")
         super().build(input_shape)
 
-    def call(self, x, seqlen=None, training=True, use_causal_mask=False, **kw):
+    def call(self, x, value=None, seqlen=None, training=True, use_causal_mask=False, **kw):
         inner = self.num_heads * self.key_dim
-        qkv = N.dense(x, self.qkv_kernel, self.qkv_bias)
-        q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
+        if value is None:
+            qkv = N.dense(x, self.qkv_kernel, self.qkv_bias)
+            q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
+        else:
+            if value.dim() != x.dim() or value.shape[-1] != x.shape[-1] or value.shape[0] != x.shape[0]:
+                raise InvalidArgumentError(
+                    "MultiHeadAttention: value must be [batch, key_len, %d] like the query (the layer projects "
+                    "both with one qkv/kernel); got query %s, value %s"
+                    % (x.shape[-1], tuple(x.shape), tuple(value.shape)))
+            q = N.dense(x, self.qkv_kernel[:, :inner].contiguous(), self.qkv_bias[:inner].contiguous())
+            kv = N.dense(value, self.qkv_kernel[:, inner:].contiguous(), self.qkv_bias[inner:].contiguous())
+            k, v = kv[..., :inner], kv[..., inner:]
         a = N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
                         self.dropout if training else 0.0, seqlen=seqlen, causal=use_causal_mask)
         return N.dense(a, self.out_kernel, self.out_bias)

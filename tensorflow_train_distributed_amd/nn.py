@@ -688,7 +688,9 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal):
         from .ops import transformer as T
         B, S, D = q.shape
-        q2, k2, v2 = [t.reshape(B * S, D).to(torch.bfloat16).contiguous() for t in (q, k, v)]
+        Sk = k.shape[1]
+        q2 = q.reshape(B * S, D).to(torch.bfloat16).contiguous()
+        k2, v2 = [t.reshape(B * Sk, D).to(torch.bfloat16).contiguous() for t in (k, v)]
         o = torch.empty_like(q2)
         lse = torch.empty((B * num_heads, S), dtype=torch.float32, device=q.device)
         rng = None
@@ -696,46 +698,58 @@ class _Attention(torch.autograd.Function):
             rng = T.RngState(_Rng.seed, q.device)
             rng.t[1] = _Rng.offset
             _Rng.offset += 1
-        T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, seqlen=seqlen, p_drop=rate, rng=rng, site=site,
+        T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, Sk=Sk, seqlen=seqlen, p_drop=rate, rng=rng, site=site,
                         causal=causal)
         ctx.save_for_backward(q2, k2, v2, o, lse, seqlen)
-        ctx.cfg = (B, S, D, num_heads, rate, rng, site, q.dtype, causal)
+        ctx.cfg = (B, S, Sk, D, num_heads, rate, rng, site, q.dtype, causal)
         return o.reshape(B, S, D).to(q.dtype)
 
     @staticmethod
     def backward(ctx, do):
         from .ops import transformer as T
         q2, k2, v2, o, lse, seqlen = ctx.saved_tensors
-        B, S, D, nh, rate, rng, site, dt, causal = ctx.cfg
+        B, S, Sk, D, nh, rate, rng, site, dt, causal = ctx.cfg
         d2 = do.reshape(B * S, D).to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2)
-        T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, seqlen=seqlen, p_drop=rate, rng=rng, site=site,
-                        causal=causal)
-        return (dq.reshape(B, S, D).to(dt), dk.reshape(B, S, D).to(dt), dv.reshape(B, S, D).to(dt),
+        T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, Sk=Sk, seqlen=seqlen, p_drop=rate, rng=rng,
+                        site=site, causal=causal)
+        return (dq.reshape(B, S, D).to(dt), dk.reshape(B, Sk, D).to(dt), dv.reshape(B, Sk, D).to(dt),
                 None, None, None, None, None)
 
 
 def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0, causal: bool = False):
-    """Multi-head scaled dot-product attention, token-major [B, S, num_heads*64] inputs,
-    keys >= seqlen[b] masked; causal=True also masks keys after the query (position s attends
-    positions <= s: a left-to-right language model). GPU: the flash kernels (head_dim 64,
-    S % 128 == 0); their causal form skips the key tiles above the diagonal."""
+    """Multi-head scaled dot-product attention, token-major inputs: q [B, S, num_heads*64], k and v
+    [B, Sk, num_heads*64]. Sk == S is self-attention; Sk != S is cross-attention over a memory of
+    another length (a decoder's attention over the encoder's output): the result has the query's
+    S rows, the gradients of k and v have Sk rows. Keys >= seqlen[b] are masked — seqlen is the
+    keys' (the memory's) valid length, at most Sk; queries are never masked. causal=True also masks
+    keys after the query (position s attends positions <= s: a left-to-right language model) and
+    needs Sk == S. GPU: the flash kernels (head_dim 64, S % 128 == 0 and Sk % 128 == 0); their
+    causal form skips the key tiles above the diagonal."""
     B, S, D = q.shape
+    Sk = k.shape[1]
     hd = D // num_heads
+    if tuple(k.shape) != (B, Sk, D) or tuple(v.shape) != (B, Sk, D):
+        raise InvalidArgumentError(
+            "ttd.nn.attention: k and v must both be [batch, key_len, width] with q's batch and width "
+            "(got q %s, k %s, v %s)" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if causal and Sk != S:
+        raise InvalidArgumentError(
+            "ttd.nn.attention: causal=True needs as many keys as queries (got %d queries, %d keys)" % (S, Sk))
     if _on_gpu(q, k, v):
-        if hd != 64 or S % 128 != 0 or D % num_heads:
+        if hd != 64 or S % 128 != 0 or Sk % 128 != 0 or D % num_heads:
             raise InvalidArgumentError(
                 "ttd.nn.attention on GPU runs the flash kernels for head_dim 64 and seq_len %% 128 == 0 "
-                "(got head_dim %s, seq_len %d); pad the sequence (and mask it with seqlen) or use 64-wide heads"
-                % (D / num_heads, S))
+                "(got head_dim %s, seq_len %d%s); pad the sequence (and mask it with seqlen) or use 64-wide heads"
+                % (D / num_heads, S, "" if Sk == S else ", key seq_len %d" % Sk))
         sl = seqlen.to(torch.int32).contiguous() if seqlen is not None else None
         return _Attention.apply(q, k, v, num_heads, float(dropout_rate), sl, int(site), bool(causal))
     qh = q.reshape(B, S, num_heads, hd).transpose(1, 2)
-    kh = k.reshape(B, S, num_heads, hd).transpose(1, 2)
-    vh = v.reshape(B, S, num_heads, hd).transpose(1, 2)
+    kh = k.reshape(B, Sk, num_heads, hd).transpose(1, 2)
+    vh = v.reshape(B, Sk, num_heads, hd).transpose(1, 2)
     sc = qh @ kh.transpose(-1, -2) / math.sqrt(hd)
     if seqlen is not None:
-        m = torch.arange(S, device=q.device)[None, :] < seqlen[:, None].long()
+        m = torch.arange(Sk, device=q.device)[None, :] < seqlen[:, None].long()
         sc = sc.masked_fill(~m[:, None, None, :], float("-inf"))
     if causal:
         tri = torch.ones((S, S), dtype=torch.bool, device=q.device).tril()

@@ -16,6 +16,8 @@ _lib.register({
     "ttdk_attn_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, P],
     "ttdk_attn_fwd_causal": [P, L, P, L, P, L, P, L, P, P, I, I, I, F, P, I, I, P],
     "ttdk_attn_bwd_causal": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, I, P],
+    "ttdk_attn_fwd_cross": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, F, P, I, I, P],
+    "ttdk_attn_bwd_cross": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, F, P, I, I, P],
     "ttdk_attn_set_fused_bwd": [I],
     "ttdk_ln_fwd": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
     "ttdk_ln_bwd_num_blocks": [I],
@@ -61,13 +63,20 @@ class RngState:
 
 
 # ------------------------------------------------------------------ attention
-def attention_fwd(q, k, v, out, lse, B, H, S, *, seqlen=None, p_drop=0.0, rng=None, site=0, causal=False):
-    """q/k/v/out: 2-D bf16 views [B*S, >= H*64] (row stride = .stride(0)); lse fp32 [B*H, S].
+def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, seqlen=None, p_drop=0.0, rng=None, site=0, causal=False):
+    """q/out: 2-D bf16 views [B*S, >= H*64], k/v: [B*Sk, >= H*64] (row stride = .stride(0), each its
+    own); lse fp32 [B*H, S]. Sk (None: S) is the key length — cross-attention over a memory of
+    another length; seqlen then holds the memory's valid lengths (keys >= seqlen[b] masked).
     causal: query s attends keys <= s only (combined with seqlen); the key tiles above the diagonal
-    are not streamed."""
-    _lib.call("ttdk_attn_fwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-              v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, float(p_drop),
-              _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
+    are not streamed. causal needs Sk == S."""
+    if Sk is None or Sk == S:
+        _lib.call("ttdk_attn_fwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, float(p_drop),
+                  _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
+    else:
+        _lib.call("ttdk_attn_fwd_cross", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, int(Sk),
+                  float(p_drop), _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
     return out, lse
 
 
@@ -76,20 +85,29 @@ def set_fused_attention_bwd(on: bool):
     at BERT-Large: attention.hip) or the split dQ / dK-dV kernels (default;
     TTD_ATTN_FUSED_BWD=1 at start-up selects the fused one). A causal backward ignores the switch:
     the fused kernel has no causal form, so attention_bwd(..., causal=True) always runs the split
-    kernels."""
+    kernels; so does a cross-attention backward (Sk != S)."""
     _lib.call("ttdk_attn_set_fused_bwd", int(bool(on)))
 
 
-def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, delta=None, seqlen=None, p_drop=0.0, rng=None,
-                  site=0, causal=False):
-    """Backward of attention_fwd with the same seqlen / p_drop / rng / site / causal."""
+def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, delta=None, seqlen=None, p_drop=0.0,
+                  rng=None, site=0, causal=False):
+    """Backward of attention_fwd with the same Sk / seqlen / p_drop / rng / site / causal. dq has the
+    query's B*S rows, dk / dv the keys' B*Sk; delta fp32 [B*H, S]. Sk != S always runs the split
+    kernels (the fused backward is a self-attention kernel)."""
     if delta is None:
         delta = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
-    _lib.call("ttdk_attn_bwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-              v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
-              delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
-              dv.stride(0), _p(seqlen), B, H, S, float(p_drop), _p(rng.t if rng is not None else None), int(site),
-              int(bool(causal)), _s())
+    if Sk is None or Sk == S:
+        _lib.call("ttdk_attn_bwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
+                  dv.stride(0), _p(seqlen), B, H, S, float(p_drop), _p(rng.t if rng is not None else None),
+                  int(site), int(bool(causal)), _s())
+    else:
+        _lib.call("ttdk_attn_bwd_cross", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
+                  dv.stride(0), _p(seqlen), B, H, S, int(Sk), float(p_drop),
+                  _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
     return dq, dk, dv
 
 
@@ -250,19 +268,22 @@ def keep_mask(seed: int, step: int, site: int, p: float, idx) -> np.ndarray:
     return h >= np.uint64(drop_threshold(p))
 
 
-def attention_keep_mask(seed: int, step: int, site: int, p: float, B: int, H: int, S: int) -> np.ndarray:
-    """Keep mask [B, H, S(query), S(key)] of the attention-probability dropout (mirror of
-    tile_common.h attn_pair_hash / attn_keep_half: keys k and k + 16 of an aligned 32-key block
-    share one hash, pair ((k >> 5) << 4) | (k & 15), 16-bit half (k >> 4) & 1)."""
+def attention_keep_mask(seed: int, step: int, site: int, p: float, B: int, H: int, S: int, Sk=None) -> np.ndarray:
+    """Keep mask [B, H, S(query), Sk(key)] (Sk None: S) of the attention-probability dropout (mirror
+    of tile_common.h attn_pair_hash / attn_keep_half: keys k and k + 16 of an aligned 32-key block
+    share one hash, pair ((k >> 5) << 4) | (k & 15), 16-bit half (k >> 4) & 1). The row id is
+    (b*H + h)*S + query and the pair term depends on the key alone, so a longer memory extends the
+    mask of a shorter one."""
+    Sk = S if Sk is None else int(Sk)
     key = np.uint64(drop_key(seed, step, site))
     thr = 0 if p <= 0 else (0x10000 if p >= 1 else int(float(np.float32(p)) * 65536.0))
     rowid = np.arange(B * H * S, dtype=np.uint64).reshape(B * H, S, 1)
-    k = np.arange(S, dtype=np.uint64).reshape(1, 1, S)
+    k = np.arange(Sk, dtype=np.uint64).reshape(1, 1, Sk)
     pair = ((k >> np.uint64(5)) << np.uint64(4)) | (k & np.uint64(15))
     mixed = ((rowid * np.uint64(0x9E3779B1)) + (pair * np.uint64(0x7FEB352D))) & M32
     h = _attn_mix(key ^ mixed)
     half = np.where(((k >> np.uint64(4)) & np.uint64(1)) == 1, h >> np.uint64(16), h & np.uint64(0xFFFF))
-    return (half >= np.uint64(thr)).reshape(B, H, S, S)
+    return (half >= np.uint64(thr)).reshape(B, H, S, Sk)
 
 
 def attention_drop_scale(p: float) -> float:

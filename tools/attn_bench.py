@@ -3,7 +3,9 @@
 without attention dropout; the backward on the single-kernel path and on the split dQ / dK-dV
 kernels. --causal times the causal kernels (split backward only: the fused kernel has no causal
 form); TTD_ATTN_CAUSAL_ORDER=natural selects their natural block order for the A/B.
-usage: python tools/attn_bench.py [B] [--causal]"""
+--kv-seq N times cross-attention: S = 512 queries over a memory of N keys (forward and the split
+backward — the fused and causal kernels are self-attention only); FLOPs 4 B H Sq Sk 64.
+usage: python tools/attn_bench.py [B] [--causal | --kv-seq N]"""
 import sys
 
 import torch
@@ -25,8 +27,16 @@ def timeit(fn, iters=20):
     return s.elapsed_time(e) / iters * 1e3
 
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-causal = "--causal" in sys.argv[1:]
+argv = sys.argv[1:]
+Sk = None
+if "--kv-seq" in argv:
+    i = argv.index("--kv-seq")
+    Sk = int(argv[i + 1])
+    del argv[i:i + 2]
+args = [a for a in argv if not a.startswith("--")]
+causal = "--causal" in argv
+if causal and Sk is not None:
+    sys.exit("--causal and --kv-seq exclude each other: the causal kernels need Sk == S")
 B, H, S, D = (int(args[0]) if args else 32), 16, 512, 64
 qkv = (torch.randn(B * S, 3 * H * D, device="cuda") * 0.5).bfloat16()
 q, k, v = qkv[:, :H * D], qkv[:, H * D:2 * H * D], qkv[:, 2 * H * D:]
@@ -35,6 +45,34 @@ lse = torch.empty(B * H, S, device="cuda")
 dout = torch.randn_like(out)
 dqkv = torch.empty_like(qkv)
 rng = T.RngState(7, "cuda")
+if Sk is not None:
+    # the memory: K / V out of a fused [B*Sk, 2*H*D] projection, dK / dV into one; Q / dQ stay
+    # views of the [B*S, 3*H*D] buffer. Goes through the cross entry points even at Sk == S.
+    kvm = (torch.randn(B * Sk, 2 * H * D, device="cuda") * 0.5).bfloat16()
+    dkvm = torch.empty_like(kvm)
+    km, vm = kvm[:, :H * D], kvm[:, H * D:]
+    fl_x = 4.0 * B * H * S * Sk * D
+    st = T._lib.stream
+
+    def xfwd(p):
+        T._lib.call("ttdk_attn_fwd_cross", q.data_ptr(), q.stride(0), km.data_ptr(), km.stride(0), vm.data_ptr(),
+                    vm.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), None, B, H, S, Sk, p,
+                    rng.t.data_ptr(), 0, 0, st())
+
+    def xbwd(p):
+        T._lib.call("ttdk_attn_bwd_cross", q.data_ptr(), q.stride(0), km.data_ptr(), km.stride(0), vm.data_ptr(),
+                    vm.stride(0), out.data_ptr(), out.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+                    delta.data_ptr(), dqkv.data_ptr(), dqkv.stride(0), dkvm.data_ptr(), dkvm.stride(0),
+                    dkvm[:, H * D:].data_ptr(), dkvm.stride(0), None, B, H, S, Sk, p, rng.t.data_ptr(), 0, 0, st())
+
+    delta = torch.empty_like(lse)
+    T.set_fused_attention_bwd(False)
+    for p in (0.0, 0.1):
+        tf = timeit(lambda: xfwd(p))
+        tb = timeit(lambda: xbwd(p))
+        print("cross Sq=%d Sk=%d p=%.1f  fwd %6.1f us %5.0f TF/s   bwd split %6.1f us %5.0f TF/s"
+              % (S, Sk, p, tf, fl_x / tf / 1e6, tb, 2.5 * fl_x / tb / 1e6))
+    sys.exit(0)
 fl_f = 4.0 * B * H * S * S * D
 kw = {"causal": True} if causal else {}
 for p in (0.0, 0.1):
