@@ -31,6 +31,30 @@
 // launch B*H*S/128 workgroups, bwd_kv B*H*Sk/128. The causal instantiations and the fused
 // backward are for Sk == S only.
 //
+// Grouped-query attention (ttdk_attn_fwd_gqa / ttdk_attn_bwd_gqa): H query heads share Hk key/value
+// heads, G = H / Hk to each (Hk == 1: multi-query attention); query head h uses key/value head
+// h / G, the layout of repeat_interleave over the head axis. K, V, dK, dV hold Hk * 64 columns and
+// are never repeated in memory. Again only the index arithmetic differs:
+//   what belongs to the query (Q, O, dO, dQ, lse / delta row bh*S + q, the dropout row id
+//                              bh*S + q) stays indexed by the query head, bh = b*H + h: the
+//                              heads of a group draw independent dropout masks;
+//   K / V tiles (fwd, bwd_q)   column (h / G) * 64; the grids stay B*H*S/128;
+//   bwd_kv                     B*Hk*Sk/128 workgroups: one owns 128 keys of ONE key/value head and
+//                              sweeps the 64-query tiles of its G query heads in turn (Q / dO
+//                              column, lse / delta rows and dropout row ids of that head), dK and
+//                              dV staying in the same register accumulators, stored once. The sum
+//                              over the group runs in fp32 in head order: no atomics, no workspace,
+//                              no second pass, the same bits every run. Causal: every head's sweep
+//                              starts at qt0 = 2 kblk with its own diagonal trip.
+// With Hk == H every kernel is the self-attention kernel: the grouped forms are template
+// instantiations of their own (GQA), so the self-attention code is unchanged — a run-time G == 1
+// cost the causal p = 0.1 backward 2 us of 573 (profiles/attn_gqa_bench.txt, section 0). The fused backward is
+// an Hk == H kernel. Locality (read off the code, not measured): xcd_remap hands each XCD one
+// contiguous run of work items, and the G * S/128 fwd / bwd_q work items of a group are
+// contiguous, so a group's heads read their shared K / V through one XCD's L2 — except the at
+// most 7 groups that straddle the end of an XCD's run (none when B*Hk is a multiple of 8). In
+// bwd_kv the group is one workgroup: K and V are read once, into registers.
+//
 // Kernels (4 waves / workgroup, XCD-aware block order so the Q-blocks of one head share an
 // L2):
 //   fwd     : 128 query rows per workgroup (32 per wave); K/V tiles of 64 keys double-buffered
@@ -88,6 +112,9 @@ struct AttnParams {
   const long long* rng;
   uint32_t site;
   int order;           // causal block order within a head: causal_block()
+  // (last, so that the fields above keep their kernarg offsets)
+  int Hk, G;           // key/value heads and G = H / Hk query heads per key/value head; Hk == H,
+                       // G == 1 unless grouped-query attention
 };
 
 __device__ __forceinline__ uint4 ldg16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
@@ -165,7 +192,11 @@ __device__ __forceinline__ int causal_block(int j, int bh, int nblk, int order, 
 // barrier). Masked scores are -inf BEFORE the row max, so a masked key adds exactly nothing to
 // m, l, O; and the running max moves per row (not for every row of a wave whose ballot fired), so
 // a row's result does not depend on keys that only other rows of its wave may see.
-template <bool DROP, bool CAUSAL = false>
+//
+// GQA (launched when Hk != H): K / V tiles from key/value head h / G; everything else as above.
+// A template parameter, not a run-time G == 1: the self-attention kernels keep their code, without
+// the integer division at the head of every workgroup's address chain.
+template <bool DROP, bool CAUSAL = false, bool GQA = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int qblocks = P.S / QBLK;
@@ -189,8 +220,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
       qf[qb][ks] = ldg_frag(P.q + (tok0 + q0 + qb * 16 + i16) * P.ldq + h * D + ks * 32 + g * 8);
 
   TileLoader lk, lv;
-  lk.init(P.k + tokk * P.ldk + h * D, P.ldk, tid);
-  lv.init(P.v + tokk * P.ldv + h * D, P.ldv, tid);
+  const int hk = GQA ? h / P.G : h;  // the key/value head of query head h
+  lk.init(P.k + tokk * P.ldk + hk * D, P.ldk, tid);
+  lv.init(P.v + tokk * P.ldv + hk * D, P.ldv, tid);
 
   float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
   f32x4_t o[2][4];
@@ -369,16 +401,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 // (32 keys from k0) whose keys all lie above the tile's last query skips the tile (no MFMA /
 // softmax work, only its share of the next tile's staging and the barrier). Every later trip
 // runs today's unmasked body. Block order: causal_block().
-template <bool DROP, int MODE = 0, bool CAUSAL = false>
+//
+// GQA (MODE 0 only; launched when Hk != H): the workgroup owns 128 keys of key/value head hk of
+// batch b (grid B*Hk*Sk/128; causal_block() and the XCD remap take b*Hk + hk) and runs the sweep
+// above once per query head h0 .. h0 + G - 1 of its group, h0 = hk * G, into the same dk / dv.
+template <bool DROP, int MODE = 0, bool CAUSAL = false, bool GQA = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   constexpr int BUF = 2 * TILE_BYTES + 2 * KT * 4;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int kblocks = P.Sk / QBLK;
   const int t = tile::xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = t / kblocks;
-  int kblk = t - bh * kblocks;
-  if constexpr (CAUSAL) kblk = causal_block(kblk, bh, kblocks, P.order, false);
-  const int b = bh / P.H, h = bh - b * P.H;
+  const int bhk = t / kblocks;  // (batch, key/value head)
+  int kblk = t - bhk * kblocks;
+  if constexpr (CAUSAL) kblk = causal_block(kblk, bhk, kblocks, P.order, false);
+  const int nkv = GQA ? P.Hk : P.H;
+  const int b = bhk / nkv, hk = bhk - b * nkv;
+  const int h0 = GQA ? hk * P.G : hk;  // first query head of the group
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int k0 = kblk * QBLK + wave * 32;
@@ -405,12 +443,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const long long row = tokk + k0 + kb * 16 + i16;
-        kf[kb][ks] = ldg_frag(P.k + row * P.ldk + h * D + ks * 32 + g * 8);
-        vf[kb][ks] = ldg_frag(P.v + row * P.ldv + h * D + ks * 32 + g * 8);
+        kf[kb][ks] = ldg_frag(P.k + row * P.ldk + hk * D + ks * 32 + g * 8);
+        vf[kb][ks] = ldg_frag(P.v + row * P.ldv + hk * D + ks * 32 + g * 8);
       }
+    // the query head being swept: h0 .. h0 + G - 1 in turn (GQA: the trip loop below moves bh, the
+    // two loaders and st_src on by one head)
+    int bh = GQA ? b * P.H + h0 : bhk;
     TileLoader lq, ld;
-    lq.init(P.q + tok0 * P.ldq + h * D, P.ldq, tid);
-    ld.init(P.dout + tok0 * P.lddo + h * D, P.lddo, tid);
+    lq.init(P.q + tok0 * P.ldq + h0 * D, P.ldq, tid);
+    ld.init(P.dout + tok0 * P.lddo + h0 * D, P.lddo, tid);
     // per-tile statistics, staged with the dropout scale folded in: lse2 - log2(1/(1-p)) (exp2
     // then gives P / (1-p), a kept probability's value) and delta * (1-p) (the product P * delta
     // unchanged). Thread t < 64 moves lse of query t, 64 <= t < 128 delta of query t - 64.
@@ -519,13 +560,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     f32x4_t sc[4][2], dp[4][2];
     // diag_c (causal): a tile of the diagonal trip — masked in pds, and skipped by a wave whose
     // keys all lie above the tile's last query (wave-uniform)
-    auto tile = [&](int qt, auto bufi_c, auto diag_c) {
+    // nq: the tile to stage meanwhile (the next one of this head, or a GQA group's next head's
+    // first), if nxt
+    auto tile = [&](int qt, int nq, bool nxt, auto bufi_c, auto diag_c) {
       constexpr int BUFI = decltype(bufi_c)::value;
       constexpr bool DIAG = decltype(diag_c)::value;
       constexpr int DV = DIAG ? 2 : 0;  // the mask's compare and select per element, per MFMA slot
       const int kd = k0 + i16 - qt * KT - 4 * g;
-      const bool nxt = qt + 1 < ntiles && !(MODE & 2);
-      if (nxt) load(qt + 1);
+      if constexpr (!GQA) {  // always the head's next tile; the two arguments are not read
+        nq = qt + 1;
+        nxt = qt + 1 < ntiles;
+      }
+      nxt = nxt && !(MODE & 2);
+      if (nxt) load(nq);
       if (!DIAG || __builtin_amdgcn_readfirstlane(k0) <= qt * KT + KT - 1) {
         const char* sQ = smem + BUFI * BUF;
         const float* sL = reinterpret_cast<const float*>(sQ + 2 * TILE_BYTES);
@@ -580,17 +627,54 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     __syncthreads();
     if constexpr ((MODE & 8) != 0) stamp[1] = __builtin_amdgcn_s_memtime();
     int qt = qt0;
-    if constexpr (CAUSAL) {
-      // the diagonal trip: waves 0, 1 (keys 0-63 of the block) mask in tile qt0 (and see all of
-      // tile qt0 + 1: its compares never hit); waves 2, 3 (keys 64-127) skip tile qt0 and mask in
-      // tile qt0 + 1
-      tile(qt, integral_constant<int, 0>{}, true_type{});
-      tile(qt + 1, integral_constant<int, 1>{}, true_type{});
-      qt += 2;
-    }
-    for (; qt < ntiles; qt += 2) {  // ntiles - qt is even
-      tile(qt, integral_constant<int, 0>{}, false_type{});
-      tile(qt + 1, integral_constant<int, 1>{}, false_type{});
+    if constexpr (!GQA) {
+      if constexpr (CAUSAL) {
+        // the diagonal trip: waves 0, 1 (keys 0-63 of the block) mask in tile qt0 (and see all of
+        // tile qt0 + 1: its compares never hit); waves 2, 3 (keys 64-127) skip tile qt0 and mask in
+        // tile qt0 + 1
+        tile(qt, 0, false, integral_constant<int, 0>{}, true_type{});
+        tile(qt + 1, 0, false, integral_constant<int, 1>{}, true_type{});
+        qt += 2;
+      }
+      for (; qt < ntiles; qt += 2) {  // ntiles - qt is even
+        tile(qt, 0, false, integral_constant<int, 0>{}, false_type{});
+        tile(qt + 1, 0, false, integral_constant<int, 1>{}, false_type{});
+      }
+    } else {
+      // Grouped-query attention: the G query heads of this key/value head in head order, each
+      // swept from qt0 to the end into the same dk / dv accumulators. A head's last tile (always
+      // in buffer 1) stages the next head's tile qt0 into buffer 0, so the register-staged
+      // prefetch and the one barrier per tile carry across the head boundary and no prologue is
+      // repeated: the loaders and st_src move on one head before that tile, bh (the dropout row
+      // ids) after it. Causal: every head's first trip is a diagonal trip.
+      int heads_left = P.G;
+      auto trip = [&](auto diag_c) {
+        const bool last = qt + 2 >= ntiles;  // this trip ends the head
+        tile(qt, qt + 1, true, integral_constant<int, 0>{}, diag_c);
+        if (last) {
+          --heads_left;
+          lq.lanep += D;
+          ld.lanep += D;
+          st_src += P.S;
+        }
+        tile(qt + 1, last ? qt0 : qt + 2, !last || heads_left > 0, integral_constant<int, 1>{}, diag_c);
+        qt = last ? qt0 : qt + 2;
+        return last;
+      };
+      // (two loop shapes for one sequence of trips, chosen by the register allocation they get:
+      // the causal kernels spill 104 / 248 bytes in the flat shape, the bidirectional one without
+      // dropout 24 bytes in the nested shape; as written every instantiation has no scratch)
+      if constexpr (CAUSAL) {
+        do {
+          bool last = trip(true_type{});
+          while (!last) last = trip(false_type{});
+          ++bh;
+        } while (heads_left > 0);
+      } else {
+        do {
+          if (trip(false_type{})) ++bh;
+        } while (heads_left > 0);
+      }
     }
     if constexpr ((MODE & 8) != 0) stamp[2] = __builtin_amdgcn_s_memtime();
   }
@@ -599,8 +683,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     const long long row = tokk + k0 + kb * 16 + i16;
-    bf16_t* pk = P.out + row * P.ld_out + h * D + 4 * g;
-    bf16_t* pv = P.out2 + row * P.ld_out2 + h * D + 4 * g;
+    bf16_t* pk = P.out + row * P.ld_out + hk * D + 4 * g;
+    bf16_t* pv = P.out2 + row * P.ld_out2 + hk * D + 4 * g;
     const bool valid = k0 + kb * 16 + i16 < len;
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
@@ -628,7 +712,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 // ------------------------------------------------------------------------------ bwd dQ
 // CAUSAL: as the forward — key tiles kt <= 2 qblk + 1 only; per wave a tile runs full, diagonal
 // (score -inf where key > query, before the exp2: P = 0 and dS = 0 exactly) or skipped.
-template <bool DROP, bool CAUSAL = false>
+// GQA: as the forward — K / V tiles from key/value head h / G.
+template <bool DROP, bool CAUSAL = false, bool GQA = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int qblocks = P.S / QBLK;
@@ -680,8 +765,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     for (int db = 0; db < 4; ++db) dq[qb][db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   TileLoader lk, lv;
-  lk.init(P.k + tokk * P.ldk + h * D, P.ldk, tid);
-  lv.init(P.v + tokk * P.ldv + h * D, P.ldv, tid);
+  const int hk = GQA ? h / P.G : h;  // the key/value head of query head h
+  lk.init(P.k + tokk * P.ldk + hk * D, P.ldk, tid);
+  lv.init(P.v + tokk * P.ldv + hk * D, P.ldv, tid);
   const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
   int ntiles = (len + KT - 1) / KT;
   if constexpr (CAUSAL) ntiles = min(ntiles, 2 * qblk + 2);
@@ -1054,11 +1140,13 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_fused_kernel(AttnParams P
   }
 }
 
-AttnParams make_params(int B, int H, int S, int Sk, const int* seqlen, float p_drop, const long long* rng,
+AttnParams make_params(int B, int H, int Hk, int S, int Sk, const int* seqlen, float p_drop, const long long* rng,
                        uint32_t site) {
   AttnParams P{};
   P.B = B;
   P.H = H;
+  P.Hk = Hk;
+  P.G = H / Hk;
   P.S = S;
   P.Sk = Sk;
   P.seqlen = seqlen;
@@ -1098,19 +1186,32 @@ using namespace ttdk;
 // Cross-attention: q / o have Sq rows per batch, k / v have Sk rows (the memory); lse is
 // [B*H][Sq]; seqlen[b] is the memory's valid length (keys >= it masked; queries are never
 // masked). Sq % 128 == 0 and Sk % 128 == 0; causal needs Sq == Sk.
-TTDK_EXPORT int ttdk_attn_fwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                    long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
-                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
-                                    int causal, hipStream_t st) {
-  if (Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) || (ldq | ldk | ldv | ldo) & 7 ||
-      !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (p_drop > 0.f && !rng))
+//
+// Grouped-query attention: k / v hold Hk heads (Hk * 64 columns), H % Hk == 0; query head h reads
+// key/value head h / (H / Hk). lse stays [B*H][Sq].
+TTDK_EXPORT int ttdk_attn_fwd_gqa(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                  long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
+                                  int H, int Hk, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
+                                  int causal, hipStream_t st) {
+  if (Hk <= 0 || H % Hk || Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) ||
+      (ldq | ldk | ldv | ldo) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
+      (p_drop > 0.f && !rng))
     return hipErrorInvalidValue;
-  AttnParams P = make_params(B, H, Sq, Sk, seqlen, p_drop, rng, site);
+  AttnParams P = make_params(B, H, Hk, Sq, Sk, seqlen, p_drop, rng, site);
   P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
   P.out = o; P.ld_out = ldo; P.lse = lse;
   dim3 grid(B * H * (Sq / QBLK)), block(256);
-  if (causal) {
-    P.order = causal_order();
+  if (causal) P.order = causal_order();
+  if (Hk != H) {
+    if (causal) {
+      if (p_drop > 0.f) hipLaunchKernelGGL((attn_fwd_kernel<true, true, true>), grid, block, 0, st, P);
+      else hipLaunchKernelGGL((attn_fwd_kernel<false, true, true>), grid, block, 0, st, P);
+    } else if (p_drop > 0.f) {
+      hipLaunchKernelGGL((attn_fwd_kernel<true, false, true>), grid, block, 0, st, P);
+    } else {
+      hipLaunchKernelGGL((attn_fwd_kernel<false, false, true>), grid, block, 0, st, P);
+    }
+  } else if (causal) {
     if (p_drop > 0.f) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, st, P);
     else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, 0, st, P);
   } else if (p_drop > 0.f) {
@@ -1119,6 +1220,14 @@ TTDK_EXPORT int ttdk_attn_fwd_cross(const bf16_t* q, long long ldq, const bf16_t
     hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, st, P);
   }
   return hipGetLastError();
+}
+
+TTDK_EXPORT int ttdk_attn_fwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                    long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
+                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
+                                    int causal, hipStream_t st) {
+  return ttdk_attn_fwd_gqa(q, ldq, k, ldk, v, ldv, o, ldo, lse, seqlen, B, H, H, Sq, Sk, p_drop, rng, site, causal,
+                           st);
 }
 
 TTDK_EXPORT int ttdk_attn_fwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
@@ -1159,23 +1268,26 @@ TTDK_EXPORT int ttdk_attn_set_fused_bwd(int on) {
 // causal != 0: the backward of ttdk_attn_fwd_cross(..., causal); split kernels only.
 // Sq != Sk (cross-attention): split kernels only as well — bwd_q over B*H*Sq/128 workgroups, then
 // bwd_kv over B*H*Sk/128; dq has Sq rows per batch, dk / dv have Sk, lse / delta are [B*H][Sq].
-TTDK_EXPORT int ttdk_attn_bwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                    long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
-                                    long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
-                                    bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
-                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
-                                    int causal, hipStream_t st) {
-  if (Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) ||
+// Hk != H (grouped-query attention): split kernels only as well — bwd_q over B*H*Sq/128
+// workgroups, bwd_kv over B*Hk*Sk/128, each summing its group's H / Hk query heads in head order;
+// k / v / dk / dv hold Hk heads, so dq/dk/dv may alias one fused [tokens, (H + 2*Hk)*64] buffer.
+TTDK_EXPORT int ttdk_attn_bwd_gqa(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                  long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
+                                  const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk,
+                                  long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int Hk,
+                                  int Sq, int Sk, float p_drop, const long long* rng, unsigned site, int causal,
+                                  hipStream_t st) {
+  if (Hk <= 0 || H % Hk || Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) ||
       (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) ||
       !aligned16(o) || !aligned16(dout) || (p_drop > 0.f && !rng))
     return hipErrorInvalidValue;
   const int S = Sq;
-  AttnParams P = make_params(B, H, Sq, Sk, seqlen, p_drop, rng, site);
+  AttnParams P = make_params(B, H, Hk, Sq, Sk, seqlen, p_drop, rng, site);
   P.q = q; P.k = k; P.v = v; P.o = o; P.dout = dout;
   P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo; P.lddo = lddo;
   P.lse = const_cast<float*>(lse);
   P.delta = delta;
-  if (!causal && Sq == Sk && attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
+  if (!causal && Sq == Sk && Hk == H && attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
     // one workgroup per (batch, head): dQ, dK, dV in one pass (attn_bwd_fused_kernel)
     P.out = dq; P.ld_out = lddq; P.out2 = dk; P.ld_out2 = lddk; P.out3 = dv; P.ld_out3 = lddv;
     const dim3 g1(B * H);
@@ -1193,22 +1305,46 @@ TTDK_EXPORT int ttdk_attn_bwd_cross(const bf16_t* q, long long ldq, const bf16_t
     }
     return hipGetLastError();
   }
-  // bwd_q owns query blocks, bwd_kv key blocks: two grid sizes when Sq != Sk
-  dim3 grid(B * H * (Sq / QBLK)), grid_kv(B * H * (Sk / QBLK)), block(256);
+  // bwd_q owns query blocks of the H query heads, bwd_kv key blocks of the Hk key/value heads: two
+  // grid sizes when Sq != Sk or Hk != H
+  dim3 grid(B * H * (Sq / QBLK)), grid_kv(B * Hk * (Sk / QBLK)), block(256);
   // dQ first: it computes delta (rowsum dO . O) on the way and stores it for dK / dV
   P.out = dq; P.ld_out = lddq; P.out2 = nullptr;
   if (causal) {
     P.order = causal_order();
-    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_q_kernel<true, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_bwd_q_kernel<false, true>), grid, block, 0, st, P);
+    if (Hk != H) {
+      if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_q_kernel<true, true, true>), grid, block, 0, st, P);
+      else hipLaunchKernelGGL((attn_bwd_q_kernel<false, true, true>), grid, block, 0, st, P);
+    } else if (p_drop > 0.f) {
+      hipLaunchKernelGGL((attn_bwd_q_kernel<true, true>), grid, block, 0, st, P);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_q_kernel<false, true>), grid, block, 0, st, P);
+    }
     P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
-    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, true>), grid, block, 0, st, P);
+    if (Hk != H) {
+      if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, true, true>), grid_kv, block, 0, st, P);
+      else hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, true, true>), grid_kv, block, 0, st, P);
+    } else if (p_drop > 0.f) {
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, true>), grid_kv, block, 0, st, P);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, true>), grid_kv, block, 0, st, P);
+    }
     return hipGetLastError();
   }
-  if (p_drop > 0.f) hipLaunchKernelGGL(attn_bwd_q_kernel<true>, grid, block, 0, st, P);
-  else hipLaunchKernelGGL(attn_bwd_q_kernel<false>, grid, block, 0, st, P);
+  if (Hk != H) {
+    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_q_kernel<true, false, true>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((attn_bwd_q_kernel<false, false, true>), grid, block, 0, st, P);
+  } else if (p_drop > 0.f) {
+    hipLaunchKernelGGL(attn_bwd_q_kernel<true>, grid, block, 0, st, P);
+  } else {
+    hipLaunchKernelGGL(attn_bwd_q_kernel<false>, grid, block, 0, st, P);
+  }
   P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
+  if (Hk != H) {  // the grouped form; the diagnostic forms below are self-attention kernels
+    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, false, true>), grid_kv, block, 0, st, P);
+    else hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, false, true>), grid_kv, block, 0, st, P);
+    return hipGetLastError();
+  }
   static const int kv_diag = [] {
     const char* e = getenv("TTD_ATTN_KV_DIAG");
     return e ? atoi(e) : 0;
@@ -1227,6 +1363,16 @@ TTDK_EXPORT int ttdk_attn_bwd_cross(const bf16_t* q, long long ldq, const bf16_t
     hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid_kv, block, 0, st, P);
   }
   return hipGetLastError();
+}
+
+TTDK_EXPORT int ttdk_attn_bwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                    long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
+                                    long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
+                                    bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
+                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
+                                    int causal, hipStream_t st) {
+  return ttdk_attn_bwd_gqa(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv,
+                           seqlen, B, H, H, Sq, Sk, p_drop, rng, site, causal, st);
 }
 
 TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,

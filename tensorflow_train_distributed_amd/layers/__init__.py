@@ -326,28 +326,39 @@ class MultiHeadAttention(Layer):
     encoder's output: the queries come from x through the first `inner` columns of qkv/kernel and
     qkv/bias, keys and values from `value` through the other 2*inner — the same variables, so
     names, counts and checkpoints do not depend on how the layer is called. seqlen is then the
-    memory's valid length; a causal mask needs Sk == S."""
+    memory's valid length; a causal mask needs Sk == S.
+    num_kv_heads (None: num_heads) is grouped-query attention, 1 multi-query attention: num_heads
+    query heads share num_kv_heads key/value heads (query head h uses h // (num_heads //
+    num_kv_heads)), and qkv/kernel shrinks to (D, inner + 2*inner_kv) columns — queries, then keys,
+    then values — with inner_kv = num_kv_heads*key_dim; the same four variables."""
     _default_name = "multi_head_attention"
 
-    def __init__(self, num_heads, key_dim=64, dropout=0.0, name=None):
+    def __init__(self, num_heads, key_dim=64, dropout=0.0, num_kv_heads=None, name=None):
         super().__init__(name)
         self.num_heads, self.key_dim, self.dropout = int(num_heads), int(key_dim), float(dropout)
+        self.num_kv_heads = self.num_heads if num_kv_heads is None else int(num_kv_heads)
+        if self.num_kv_heads <= 0 or self.num_heads % self.num_kv_heads:
+            raise InvalidArgumentError(
+                "MultiHeadAttention: num_heads must be a multiple of num_kv_heads (got num_heads %d, num_kv_heads %d)"
+                % (self.num_heads, self.num_kv_heads))
 
     def build(self, input_shape):
         D = input_shape[-1]
         inner = self.num_heads * self.key_dim
+        inner_kv = self.num_kv_heads * self.key_dim
         init = I.TruncatedNormal(stddev=0.02)
-        self.add_weight("qkv/kernel", (D, 3 * inner), init, attr="qkv_kernel")
-        self.add_weight("qkv/bias", (3 * inner,), "zeros", attr="qkv_bias")
+        self.add_weight("qkv/kernel", (D, inner + 2 * inner_kv), init, attr="qkv_kernel")
+        self.add_weight("qkv/bias", (inner + 2 * inner_kv,), "zeros", attr="qkv_bias")
         self.add_weight("output/kernel", (inner, D), init, attr="out_kernel")
         self.add_weight("output/bias", (D,), "zeros", attr="out_bias")
         super().build(input_shape)
 
     def call(self, x, value=None, seqlen=None, training=True, use_causal_mask=False, **kw):
         inner = self.num_heads * self.key_dim
+        inner_kv = self.num_kv_heads * self.key_dim
         if value is None:
             qkv = N.dense(x, self.qkv_kernel, self.qkv_bias)
-            q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
+            q, k, v = qkv[..., :inner], qkv[..., inner:inner + inner_kv], qkv[..., inner + inner_kv:]
         else:
             if value.dim() != x.dim() or value.shape[-1] != x.shape[-1] or value.shape[0] != x.shape[0]:
                 raise InvalidArgumentError(
@@ -356,9 +367,10 @@ class MultiHeadAttention(Layer):
                     % (x.shape[-1], tuple(x.shape), tuple(value.shape)))
             q = N.dense(x, self.qkv_kernel[:, :inner].contiguous(), self.qkv_bias[:inner].contiguous())
             kv = N.dense(value, self.qkv_kernel[:, inner:].contiguous(), self.qkv_bias[inner:].contiguous())
-            k, v = kv[..., :inner], kv[..., inner:]
+            k, v = kv[..., :inner_kv], kv[..., inner_kv:]
         a = N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
-                        self.dropout if training else 0.0, seqlen=seqlen, causal=use_causal_mask)
+                        self.dropout if training else 0.0, seqlen=seqlen, causal=use_causal_mask,
+                        num_kv_heads=self.num_kv_heads)
         return N.dense(a, self.out_kernel, self.out_bias)
 
 

@@ -19,6 +19,7 @@ accumulation) for either input dtype.
     ttd.nn.dense(x, kernel, bias, activation="relu")      # kernel [in, out] (TF layout)
     ttd.nn.conv2d(x, kernel, strides, padding)            # NHWC, kernel [R, S, C, K]
     ttd.nn.attention(q, k, v, num_heads, dropout_rate)    # [B, S, H*64] token-major
+    ttd.nn.attention(q, k, v, 16, num_kv_heads=4)         # grouped-query: k, v [B, Sk, 4*64]
 """
 from __future__ import annotations
 
@@ -685,12 +686,12 @@ def global_avg_pool(x):
 # ------------------------------------------------------------------ attention
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal):
+    def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal, num_kv_heads):
         from .ops import transformer as T
         B, S, D = q.shape
-        Sk = k.shape[1]
+        Sk, Dk = k.shape[1], k.shape[2]  # Dk = num_kv_heads * 64: narrower than D when heads are grouped
         q2 = q.reshape(B * S, D).to(torch.bfloat16).contiguous()
-        k2, v2 = [t.reshape(B * Sk, D).to(torch.bfloat16).contiguous() for t in (k, v)]
+        k2, v2 = [t.reshape(B * Sk, Dk).to(torch.bfloat16).contiguous() for t in (k, v)]
         o = torch.empty_like(q2)
         lse = torch.empty((B * num_heads, S), dtype=torch.float32, device=q.device)
         rng = None
@@ -698,41 +699,54 @@ class _Attention(torch.autograd.Function):
             rng = T.RngState(_Rng.seed, q.device)
             rng.t[1] = _Rng.offset
             _Rng.offset += 1
-        T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, Sk=Sk, seqlen=seqlen, p_drop=rate, rng=rng, site=site,
-                        causal=causal)
+        T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, Sk=Sk, Hk=num_kv_heads, seqlen=seqlen, p_drop=rate,
+                        rng=rng, site=site, causal=causal)
         ctx.save_for_backward(q2, k2, v2, o, lse, seqlen)
-        ctx.cfg = (B, S, Sk, D, num_heads, rate, rng, site, q.dtype, causal)
+        ctx.cfg = (B, S, Sk, D, Dk, num_heads, num_kv_heads, rate, rng, site, q.dtype, causal)
         return o.reshape(B, S, D).to(q.dtype)
 
     @staticmethod
     def backward(ctx, do):
         from .ops import transformer as T
         q2, k2, v2, o, lse, seqlen = ctx.saved_tensors
-        B, S, Sk, D, nh, rate, rng, site, dt, causal = ctx.cfg
+        B, S, Sk, D, Dk, nh, nkv, rate, rng, site, dt, causal = ctx.cfg
         d2 = do.reshape(B * S, D).to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2)
-        T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, Sk=Sk, seqlen=seqlen, p_drop=rate, rng=rng,
-                        site=site, causal=causal)
-        return (dq.reshape(B, S, D).to(dt), dk.reshape(B, Sk, D).to(dt), dv.reshape(B, Sk, D).to(dt),
-                None, None, None, None, None)
+        T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, Sk=Sk, Hk=nkv, seqlen=seqlen, p_drop=rate,
+                        rng=rng, site=site, causal=causal)
+        return (dq.reshape(B, S, D).to(dt), dk.reshape(B, Sk, Dk).to(dt), dv.reshape(B, Sk, Dk).to(dt),
+                None, None, None, None, None, None)
 
 
-def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0, causal: bool = False):
+def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0, causal: bool = False,
+              num_kv_heads: Optional[int] = None):
     """Multi-head scaled dot-product attention, token-major inputs: q [B, S, num_heads*64], k and v
-    [B, Sk, num_heads*64]. Sk == S is self-attention; Sk != S is cross-attention over a memory of
+    [B, Sk, num_kv_heads*64]. Sk == S is self-attention; Sk != S is cross-attention over a memory of
     another length (a decoder's attention over the encoder's output): the result has the query's
     S rows, the gradients of k and v have Sk rows. Keys >= seqlen[b] are masked — seqlen is the
     keys' (the memory's) valid length, at most Sk; queries are never masked. causal=True also masks
     keys after the query (position s attends positions <= s: a left-to-right language model) and
     needs Sk == S. GPU: the flash kernels (head_dim 64, S % 128 == 0 and Sk % 128 == 0); their
-    causal form skips the key tiles above the diagonal."""
+    causal form skips the key tiles above the diagonal.
+    num_kv_heads (None: num_heads) is grouped-query attention, num_kv_heads=1 multi-query attention:
+    num_heads % num_kv_heads == 0 and query head h attends key/value head h // (num_heads //
+    num_kv_heads) — the heads of a group are contiguous, as torch.repeat_interleave over the head
+    axis lays them out. k and v are never repeated in memory, and their gradients come back
+    num_kv_heads*64 wide, each key/value head the sum over the query heads of its group."""
     B, S, D = q.shape
     Sk = k.shape[1]
     hd = D // num_heads
-    if tuple(k.shape) != (B, Sk, D) or tuple(v.shape) != (B, Sk, D):
+    nkv = int(num_heads) if num_kv_heads is None else int(num_kv_heads)
+    if nkv <= 0 or num_heads % nkv:
         raise InvalidArgumentError(
-            "ttd.nn.attention: k and v must both be [batch, key_len, width] with q's batch and width "
-            "(got q %s, k %s, v %s)" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+            "ttd.nn.attention: num_heads must be a multiple of num_kv_heads (got num_heads %d, num_kv_heads %d)"
+            % (num_heads, nkv))
+    Dk = nkv * hd
+    if tuple(k.shape) != (B, Sk, Dk) or tuple(v.shape) != (B, Sk, Dk):
+        raise InvalidArgumentError(
+            "ttd.nn.attention: k and v must both be [batch, key_len, num_kv_heads * head_dim = %d] with q's batch "
+            "(got q %s, k %s, v %s, num_heads %d, num_kv_heads %d)"
+            % (Dk, tuple(q.shape), tuple(k.shape), tuple(v.shape), num_heads, nkv))
     if causal and Sk != S:
         raise InvalidArgumentError(
             "ttd.nn.attention: causal=True needs as many keys as queries (got %d queries, %d keys)" % (S, Sk))
@@ -743,10 +757,14 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
                 "(got head_dim %s, seq_len %d%s); pad the sequence (and mask it with seqlen) or use 64-wide heads"
                 % (D / num_heads, S, "" if Sk == S else ", key seq_len %d" % Sk))
         sl = seqlen.to(torch.int32).contiguous() if seqlen is not None else None
-        return _Attention.apply(q, k, v, num_heads, float(dropout_rate), sl, int(site), bool(causal))
+        return _Attention.apply(q, k, v, num_heads, float(dropout_rate), sl, int(site), bool(causal), nkv)
     qh = q.reshape(B, S, num_heads, hd).transpose(1, 2)
-    kh = k.reshape(B, Sk, num_heads, hd).transpose(1, 2)
-    vh = v.reshape(B, Sk, num_heads, hd).transpose(1, 2)
+    kh = k.reshape(B, Sk, nkv, hd).transpose(1, 2)
+    vh = v.reshape(B, Sk, nkv, hd).transpose(1, 2)
+    if nkv != num_heads:
+        # grouped heads: repeated inside the computation, so autograd sums each group's gradients
+        kh = kh.repeat_interleave(num_heads // nkv, dim=1)
+        vh = vh.repeat_interleave(num_heads // nkv, dim=1)
     sc = qh @ kh.transpose(-1, -2) / math.sqrt(hd)
     if seqlen is not None:
         m = torch.arange(Sk, device=q.device)[None, :] < seqlen[:, None].long()

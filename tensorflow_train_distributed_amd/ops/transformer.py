@@ -18,6 +18,8 @@ _lib.register({
     "ttdk_attn_bwd_causal": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, I, P],
     "ttdk_attn_fwd_cross": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, F, P, I, I, P],
     "ttdk_attn_bwd_cross": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, F, P, I, I, P],
+    "ttdk_attn_fwd_gqa": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, I, P],
+    "ttdk_attn_bwd_gqa": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, I, P],
     "ttdk_attn_set_fused_bwd": [I],
     "ttdk_ln_fwd": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
     "ttdk_ln_bwd_num_blocks": [I],
@@ -63,13 +65,22 @@ class RngState:
 
 
 # ------------------------------------------------------------------ attention
-def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, seqlen=None, p_drop=0.0, rng=None, site=0, causal=False):
-    """q/out: 2-D bf16 views [B*S, >= H*64], k/v: [B*Sk, >= H*64] (row stride = .stride(0), each its
+def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, p_drop=0.0, rng=None, site=0,
+                  causal=False):
+    """q/out: 2-D bf16 views [B*S, >= H*64], k/v: [B*Sk, >= Hk*64] (row stride = .stride(0), each its
     own); lse fp32 [B*H, S]. Sk (None: S) is the key length — cross-attention over a memory of
     another length; seqlen then holds the memory's valid lengths (keys >= seqlen[b] masked).
     causal: query s attends keys <= s only (combined with seqlen); the key tiles above the diagonal
-    are not streamed. causal needs Sk == S."""
-    if Sk is None or Sk == S:
+    are not streamed. causal needs Sk == S.
+    Hk (None: H) is the number of key/value heads — grouped-query attention (Hk == 1: multi-query):
+    H % Hk == 0 and query head h reads key/value head h // (H // Hk), the layout of
+    repeat_interleave over the head axis."""
+    if Hk is not None and Hk != H:
+        _lib.call("ttdk_attn_fwd_gqa", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, int(Hk), S,
+                  int(S if Sk is None else Sk), float(p_drop), _p(rng.t if rng is not None else None), int(site),
+                  int(bool(causal)), _s())
+    elif Sk is None or Sk == S:
         _lib.call("ttdk_attn_fwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
                   v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, float(p_drop),
                   _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
@@ -85,18 +96,26 @@ def set_fused_attention_bwd(on: bool):
     at BERT-Large: attention.hip) or the split dQ / dK-dV kernels (default;
     TTD_ATTN_FUSED_BWD=1 at start-up selects the fused one). A causal backward ignores the switch:
     the fused kernel has no causal form, so attention_bwd(..., causal=True) always runs the split
-    kernels; so does a cross-attention backward (Sk != S)."""
+    kernels; so does a cross-attention backward (Sk != S) and a grouped-query one (Hk != H)."""
     _lib.call("ttdk_attn_set_fused_bwd", int(bool(on)))
 
 
-def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, delta=None, seqlen=None, p_drop=0.0,
-                  rng=None, site=0, causal=False):
-    """Backward of attention_fwd with the same Sk / seqlen / p_drop / rng / site / causal. dq has the
-    query's B*S rows, dk / dv the keys' B*Sk; delta fp32 [B*H, S]. Sk != S always runs the split
-    kernels (the fused backward is a self-attention kernel)."""
+def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=None, delta=None, seqlen=None,
+                  p_drop=0.0, rng=None, site=0, causal=False):
+    """Backward of attention_fwd with the same Sk / Hk / seqlen / p_drop / rng / site / causal. dq has
+    the query's B*S rows, dk / dv the keys' B*Sk; delta fp32 [B*H, S]. Sk != S always runs the split
+    kernels (the fused backward is a self-attention kernel), and so does Hk != H: dk / dv then have
+    Hk*64 columns, each key/value head the sum over its H // Hk query heads — summed in fp32
+    registers in head order (deterministic), rounded to bf16 once."""
     if delta is None:
         delta = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
-    if Sk is None or Sk == S:
+    if Hk is not None and Hk != H:
+        _lib.call("ttdk_attn_bwd_gqa", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
+                  dv.stride(0), _p(seqlen), B, H, int(Hk), S, int(S if Sk is None else Sk), float(p_drop),
+                  _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
+    elif Sk is None or Sk == S:
         _lib.call("ttdk_attn_bwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
                   v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
                   delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
@@ -273,7 +292,9 @@ def attention_keep_mask(seed: int, step: int, site: int, p: float, B: int, H: in
     of tile_common.h attn_pair_hash / attn_keep_half: keys k and k + 16 of an aligned 32-key block
     share one hash, pair ((k >> 5) << 4) | (k & 15), 16-bit half (k >> 4) & 1). The row id is
     (b*H + h)*S + query and the pair term depends on the key alone, so a longer memory extends the
-    mask of a shorter one."""
+    mask of a shorter one. The mask is per QUERY head: with grouped-query attention (Hk < H
+    key/value heads) H is still the number of query heads, and the heads of a group draw
+    independent masks over their shared keys."""
     Sk = S if Sk is None else int(Sk)
     key = np.uint64(drop_key(seed, step, site))
     thr = 0 if p <= 0 else (0x10000 if p >= 1 else int(float(np.float32(p)) * 65536.0))

@@ -5,7 +5,11 @@ kernels. --causal times the causal kernels (split backward only: the fused kerne
 form); TTD_ATTN_CAUSAL_ORDER=natural selects their natural block order for the A/B.
 --kv-seq N times cross-attention: S = 512 queries over a memory of N keys (forward and the split
 backward — the fused and causal kernels are self-attention only); FLOPs 4 B H Sq Sk 64.
-usage: python tools/attn_bench.py [B] [--causal | --kv-seq N]"""
+--kv-heads N times grouped-query attention: the 16 query heads over N key/value heads (N = 1:
+multi-query), K / V column slices of a fused [B*S, (16 + 2*N)*64] buffer, forward and the split
+backward, with --causal as well; N = 16 is self-attention through the same buffers. The FLOPs
+do not depend on N.
+usage: python tools/attn_bench.py [B] [--causal | --kv-seq N] [--kv-heads N]"""
 import sys
 
 import torch
@@ -33,11 +37,38 @@ if "--kv-seq" in argv:
     i = argv.index("--kv-seq")
     Sk = int(argv[i + 1])
     del argv[i:i + 2]
+Hk = None
+if "--kv-heads" in argv:
+    i = argv.index("--kv-heads")
+    Hk = int(argv[i + 1])
+    del argv[i:i + 2]
 args = [a for a in argv if not a.startswith("--")]
 causal = "--causal" in argv
 if causal and Sk is not None:
     sys.exit("--causal and --kv-seq exclude each other: the causal kernels need Sk == S")
+if Hk is not None and Sk is not None:
+    sys.exit("--kv-heads and --kv-seq exclude each other")
 B, H, S, D = (int(args[0]) if args else 32), 16, 512, 64
+if Hk is not None:
+    if Hk <= 0 or H % Hk:
+        sys.exit("--kv-heads must divide %d" % H)
+    gqkv = (torch.randn(B * S, (H + 2 * Hk) * D, device="cuda") * 0.5).bfloat16()
+    gq, gk, gv = gqkv[:, :H * D], gqkv[:, H * D:(H + Hk) * D], gqkv[:, (H + Hk) * D:]
+    gd = torch.empty_like(gqkv)
+    gdq, gdk, gdv = gd[:, :H * D], gd[:, H * D:(H + Hk) * D], gd[:, (H + Hk) * D:]
+    gout = torch.empty(B * S, H * D, device="cuda", dtype=torch.bfloat16)
+    glse = torch.empty(B * H, S, device="cuda")
+    gdout = torch.randn_like(gout)
+    grng = T.RngState(7, "cuda")
+    fl_g = 4.0 * B * H * S * S * D
+    T.set_fused_attention_bwd(False)
+    for p in (0.0, 0.1):
+        kw = dict(Hk=Hk, p_drop=p, rng=grng, causal=causal)
+        tf = timeit(lambda: T.attention_fwd(gq, gk, gv, gout, glse, B, H, S, **kw))
+        tb = timeit(lambda: T.attention_bwd(gq, gk, gv, gout, gdout, glse, gdq, gdk, gdv, B, H, S, **kw))
+        print("%skv-heads %2d p=%.1f  fwd %6.1f us %5.0f TF/s   bwd split %6.1f us %5.0f TF/s"
+              % ("causal " if causal else "", Hk, p, tf, fl_g / tf / 1e6, tb, 2.5 * fl_g / tb / 1e6))
+    sys.exit(0)
 qkv = (torch.randn(B * S, 3 * H * D, device="cuda") * 0.5).bfloat16()
 q, k, v = qkv[:, :H * D], qkv[:, H * D:2 * H * D], qkv[:, 2 * H * D:]
 out = torch.empty(B * S, H * D, device="cuda", dtype=torch.bfloat16)
