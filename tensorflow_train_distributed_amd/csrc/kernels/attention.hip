@@ -18,7 +18,10 @@
 // heavy-first order the causal kernels gain 6 % at most (profiles/attn_causal_bench.txt).
 //
 //
-// Cross-attention (ttdk_attn_fwd_cross / ttdk_attn_bwd_cross): the query length S and the key
+// One exported pair, ttdk_attn_fwd / ttdk_attn_bwd, takes every form below (B, H, Hk, Sq, Sk, causal);
+// self-attention is Hk == H, Sk == Sq. The host code picks the instantiation from a table.
+//
+// Cross-attention (Sk != Sq): the query length S and the key
 // length Sk are separate (a decoder's attention over an encoder's output). Every kernel owns
 // 128 rows of one kind and streams 64-row tiles of the other, so only the index arithmetic
 // tells them apart:
@@ -31,7 +34,7 @@
 // launch B*H*S/128 workgroups, bwd_kv B*H*Sk/128. The causal instantiations and the fused
 // backward are for Sk == S only.
 //
-// Grouped-query attention (ttdk_attn_fwd_gqa / ttdk_attn_bwd_gqa): H query heads share Hk key/value
+// Grouped-query attention (Hk != H): H query heads share Hk key/value
 // heads, G = H / Hk to each (Hk == 1: multi-query attention); query head h uses key/value head
 // h / G, the layout of repeat_interleave over the head axis. K, V, dK, dV hold Hk * 64 columns and
 // are never repeated in memory. Again only the index arithmetic differs:
@@ -73,6 +76,7 @@
 //             at BERT-Large's S = 512 (occupancy: see ttdk_attn_set_fused_bwd).
 #include "tile_common.h"
 
+#include <initializer_list>
 #include <type_traits>
 
 namespace ttdk {
@@ -393,7 +397,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 // bit 1 the per-tile Q / dO reloads, bit 2 the per-tile barrier (only with bit 1) — wrong
 // results, for attributing the kernel's time; bit 3 writes per-workgroup clock stamps (entry,
 // prologue done, loop done, exit as s_memtime; entry / exit as s_memrealtime) over dV as
-// int64[grid][8] instead of dV (tools/attn_kv_stamps.py).
+// int64[grid][8] instead of dV (the script that read them is not in the tree).
 //
 // CAUSAL (MODE 0 only): the query-tile loop starts at qt0 = 2 kblk (even, so the two-buffer trip
 // structure holds); the two tiles of the first trip cross the block's diagonal and run the
@@ -1160,8 +1164,6 @@ AttnParams make_params(int B, int H, int Hk, int S, int Sk, const int* seqlen, f
   return P;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // Block order of the causal grids (causal_block()): rotated unless TTD_ATTN_CAUSAL_ORDER is
 // "natural" or "heavy" (kept for the A/B in profiles/attn_causal_bench.txt).
 int causal_order() {
@@ -1174,222 +1176,154 @@ int causal_order() {
   return v;
 }
 
-}  // namespace
-}  // namespace ttdk
-
-using namespace ttdk;
-
-// Shapes: S % 128 == 0, head_dim 64, every ld % 8 == 0 and bases 16-B aligned (checked).
-// Returns hipErrorInvalidValue on violation (the Python wrapper raises).
-// causal != 0: query q attends keys k <= q (and k < seqlen[b]).
-//
-// Cross-attention: q / o have Sq rows per batch, k / v have Sk rows (the memory); lse is
-// [B*H][Sq]; seqlen[b] is the memory's valid length (keys >= it masked; queries are never
-// masked). Sq % 128 == 0 and Sk % 128 == 0; causal needs Sq == Sk.
-//
-// Grouped-query attention: k / v hold Hk heads (Hk * 64 columns), H % Hk == 0; query head h reads
-// key/value head h / (H / Hk). lse stays [B*H][Sq].
-TTDK_EXPORT int ttdk_attn_fwd_gqa(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                  long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
-                                  int H, int Hk, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
-                                  int causal, hipStream_t st) {
-  if (Hk <= 0 || H % Hk || Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) ||
-      (ldq | ldk | ldv | ldo) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) ||
+// What both entry points refuse: lds is the OR of every leading dimension of the call, bases the
+// pointers that have to be 16-byte aligned.
+bool args_ok(int H, int Hk, int Sq, int Sk, int causal, float p_drop, const long long* rng, long long lds,
+             std::initializer_list<const void*> bases) {
+  if (Hk <= 0 || H % Hk || Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) || (lds & 7) ||
       (p_drop > 0.f && !rng))
-    return hipErrorInvalidValue;
-  AttnParams P = make_params(B, H, Hk, Sq, Sk, seqlen, p_drop, rng, site);
-  P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
-  P.out = o; P.ld_out = ldo; P.lse = lse;
-  dim3 grid(B * H * (Sq / QBLK)), block(256);
-  if (causal) P.order = causal_order();
-  if (Hk != H) {
-    if (causal) {
-      if (p_drop > 0.f) hipLaunchKernelGGL((attn_fwd_kernel<true, true, true>), grid, block, 0, st, P);
-      else hipLaunchKernelGGL((attn_fwd_kernel<false, true, true>), grid, block, 0, st, P);
-    } else if (p_drop > 0.f) {
-      hipLaunchKernelGGL((attn_fwd_kernel<true, false, true>), grid, block, 0, st, P);
-    } else {
-      hipLaunchKernelGGL((attn_fwd_kernel<false, false, true>), grid, block, 0, st, P);
-    }
-  } else if (causal) {
-    if (p_drop > 0.f) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, 0, st, P);
-  } else if (p_drop > 0.f) {
-    hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, st, P);
-  } else {
-    hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, st, P);
-  }
-  return hipGetLastError();
+    return false;
+  for (const void* p : bases)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+  return true;
 }
 
-TTDK_EXPORT int ttdk_attn_fwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                    long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
-                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
-                                    int causal, hipStream_t st) {
-  return ttdk_attn_fwd_gqa(q, ldq, k, ldk, v, ldv, o, ldo, lse, seqlen, B, H, H, Sq, Sk, p_drop, rng, site, causal,
-                           st);
+// Every instantiation that is launched, indexed [gqa][causal][drop] (gqa: Hk != H).
+using AttnKernel = void (*)(AttnParams);
+
+constexpr AttnKernel kFwd[2][2][2] = {
+    {{attn_fwd_kernel<false, false, false>, attn_fwd_kernel<true, false, false>},
+     {attn_fwd_kernel<false, true, false>, attn_fwd_kernel<true, true, false>}},
+    {{attn_fwd_kernel<false, false, true>, attn_fwd_kernel<true, false, true>},
+     {attn_fwd_kernel<false, true, true>, attn_fwd_kernel<true, true, true>}}};
+
+constexpr AttnKernel kBwdQ[2][2][2] = {
+    {{attn_bwd_q_kernel<false, false, false>, attn_bwd_q_kernel<true, false, false>},
+     {attn_bwd_q_kernel<false, true, false>, attn_bwd_q_kernel<true, true, false>}},
+    {{attn_bwd_q_kernel<false, false, true>, attn_bwd_q_kernel<true, false, true>},
+     {attn_bwd_q_kernel<false, true, true>, attn_bwd_q_kernel<true, true, true>}}};
+
+constexpr AttnKernel kBwdKv[2][2][2] = {
+    {{attn_bwd_kv_kernel<false, 0, false, false>, attn_bwd_kv_kernel<true, 0, false, false>},
+     {attn_bwd_kv_kernel<false, 0, true, false>, attn_bwd_kv_kernel<true, 0, true, false>}},
+    {{attn_bwd_kv_kernel<false, 0, false, true>, attn_bwd_kv_kernel<true, 0, false, true>},
+     {attn_bwd_kv_kernel<false, 0, true, true>, attn_bwd_kv_kernel<true, 0, true, true>}}};
+
+// TTD_ATTN_KV_DIAG=<mode>: the diagnostic forms of bwd_kv (MODE above). They are self-attention
+// dropout kernels: honoured only for Hk == H, non-causal, p_drop > 0; any other value runs MODE 0.
+struct KvDiag {
+  int mode;
+  AttnKernel kernel;
+};
+constexpr KvDiag kKvDiag[] = {
+    {1, attn_bwd_kv_kernel<true, 1>}, {2, attn_bwd_kv_kernel<true, 2>}, {6, attn_bwd_kv_kernel<true, 6>},
+    {7, attn_bwd_kv_kernel<true, 7>}, {8, attn_bwd_kv_kernel<true, 8>}, {15, attn_bwd_kv_kernel<true, 15>}};
+
+int kv_diag() {
+  static const int v = [] {
+    const char* e = getenv("TTD_ATTN_KV_DIAG");
+    return e ? atoi(e) : 0;
+  }();
+  return v;
 }
 
-TTDK_EXPORT int ttdk_attn_fwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                     long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B,
-                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
-                                     hipStream_t st) {
-  return ttdk_attn_fwd_cross(q, ldq, k, ldk, v, ldv, o, ldo, lse, seqlen, B, H, S, S, p_drop, rng, site, causal, st);
-}
+// Single-kernel backward (attn_bwd_fused_kernel), one workgroup per (batch, head), for these S only;
+// kernel[drop]. S = 512: 8 waves x 64 keys (two waves per SIMD); S = 256 / 128: 4 waves x 64 / 32.
+struct FusedBwd {
+  int S, threads;
+  AttnKernel kernel[2];
+};
+constexpr FusedBwd kFusedBwd[] = {
+    {128, 256, {attn_bwd_fused_kernel<2, 4, false>, attn_bwd_fused_kernel<2, 4, true>}},
+    {256, 256, {attn_bwd_fused_kernel<4, 4, false>, attn_bwd_fused_kernel<4, 4, true>}},
+    {512, 512, {attn_bwd_fused_kernel<4, 8, false>, attn_bwd_fused_kernel<4, 8, true>}}};
 
-TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                              long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B, int H,
-                              int S, float p_drop, const long long* rng, unsigned site, hipStream_t st) {
-  return ttdk_attn_fwd_causal(q, ldq, k, ldk, v, ldv, o, ldo, lse, seqlen, B, H, S, p_drop, rng, site, 0, st);
-}
-
-// Single-kernel backward (attn_bwd_fused_kernel) for S in {128, 256, 512}: opt-in
-// (TTD_ATTN_FUSED_BWD=1 or ttdk_attn_set_fused_bwd(1)). Measured at BERT-Large b128 (S = 512,
-// p = 0.1): 1190 us standalone vs 980 us for the split dQ / dK-dV kernels, BERT step 185.2 vs
-// 177.2 ms — one workgroup per (b, h) holds 4 waves (the S = 512 dK^T / dV^T accumulators need
-// 256 AGPRs per lane: one wave per SIMD, LDS 145 KB: one workgroup per CU), too little
-// occupancy to hide the MFMA -> softmax dependencies; the 8-wave form spills 65 VGPRs.
-// The fused kernel has no causal form: a causal backward always runs the split kernels, whatever
-// this switch says.
-static int g_attn_fused = -1;
-static bool attn_fused_bwd() {
+// The fused backward is opt-in (TTD_ATTN_FUSED_BWD=1 or ttdk_attn_set_fused_bwd(1)). Measured at
+// BERT-Large b128 (S = 512, p = 0.1): 1190 us standalone vs 980 us for the split dQ / dK-dV
+// kernels, BERT step 185.2 vs 177.2 ms — one workgroup per (b, h) holds 4 waves (the S = 512
+// dK^T / dV^T accumulators need 256 AGPRs per lane: one wave per SIMD, LDS 145 KB: one workgroup
+// per CU), too little occupancy to hide the MFMA -> softmax dependencies; the 8-wave form spills
+// 65 VGPRs.
+int g_attn_fused = -1;
+bool attn_fused_bwd() {
   if (g_attn_fused < 0) {
     const char* e = getenv("TTD_ATTN_FUSED_BWD");
     g_attn_fused = (e != nullptr && e[0] == '1') ? 1 : 0;
   }
   return g_attn_fused != 0;
 }
+
+}  // namespace
+}  // namespace ttdk
+
+using namespace ttdk;
+
+// The one forward / backward pair: self-attention is Hk == H, Sq == Sk.
+// Shapes: head_dim 64, Sq % 128 == 0 and Sk % 128 == 0, every ld % 8 == 0 and bases 16-B aligned
+// (checked). Returns hipErrorInvalidValue on violation (the Python wrapper raises).
+// q / o have Sq rows per batch, k / v have Sk rows (cross-attention: the memory); lse is
+// [B*H][Sq]; seqlen[b] is the keys' valid length (keys >= it masked; queries are never masked).
+// causal != 0: query q attends keys k <= q (and k < seqlen[b]); needs Sq == Sk.
+// Grouped-query attention: k / v hold Hk heads (Hk * 64 columns), H % Hk == 0; query head h reads
+// key/value head h / (H / Hk). lse stays [B*H][Sq].
+TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                              long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B, int H,
+                              int Hk, int Sq, int Sk, float p_drop, const long long* rng, unsigned site, int causal,
+                              hipStream_t st) {
+  if (!args_ok(H, Hk, Sq, Sk, causal, p_drop, rng, ldq | ldk | ldv | ldo, {q, k, v, o})) return hipErrorInvalidValue;
+  AttnParams P = make_params(B, H, Hk, Sq, Sk, seqlen, p_drop, rng, site);
+  P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
+  P.out = o; P.ld_out = ldo; P.lse = lse;
+  if (causal) P.order = causal_order();
+  hipLaunchKernelGGL(kFwd[Hk != H][causal != 0][p_drop > 0.f], dim3(B * H * (Sq / QBLK)), dim3(256), 0, st, P);
+  return hipGetLastError();
+}
+
 TTDK_EXPORT int ttdk_attn_set_fused_bwd(int on) {
   g_attn_fused = on ? 1 : 0;
   return 0;
 }
 
-// dq/dk/dv may alias one fused [tokens, 3*H*64] buffer (different column offsets).
-// causal != 0: the backward of ttdk_attn_fwd_cross(..., causal); split kernels only.
-// Sq != Sk (cross-attention): split kernels only as well — bwd_q over B*H*Sq/128 workgroups, then
-// bwd_kv over B*H*Sk/128; dq has Sq rows per batch, dk / dv have Sk, lse / delta are [B*H][Sq].
-// Hk != H (grouped-query attention): split kernels only as well — bwd_q over B*H*Sq/128
-// workgroups, bwd_kv over B*Hk*Sk/128, each summing its group's H / Hk query heads in head order;
-// k / v / dk / dv hold Hk heads, so dq/dk/dv may alias one fused [tokens, (H + 2*Hk)*64] buffer.
-TTDK_EXPORT int ttdk_attn_bwd_gqa(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                  long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
-                                  const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk,
-                                  long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int Hk,
-                                  int Sq, int Sk, float p_drop, const long long* rng, unsigned site, int causal,
-                                  hipStream_t st) {
-  if (Hk <= 0 || H % Hk || Sq <= 0 || Sk <= 0 || Sq % QBLK || Sk % QBLK || (causal && Sq != Sk) ||
-      (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7 || !aligned16(q) || !aligned16(k) || !aligned16(v) ||
-      !aligned16(o) || !aligned16(dout) || (p_drop > 0.f && !rng))
+// The backward of ttdk_attn_fwd with the same arguments. dq has Sq rows per batch, dk / dv have Sk
+// rows and Hk heads; lse / delta are [B*H][Sq]. dq / dk / dv may alias one fused
+// [tokens, (H + 2*Hk)*64] buffer (different column offsets).
+// Split kernels: bwd_q over B*H*Sq/128 workgroups (the query blocks of the H query heads), then
+// bwd_kv over B*Hk*Sk/128 (the key blocks of the Hk key/value heads, each summing its group's
+// H / Hk query heads in head order). The fused kernel, when switched on, takes only what it has a
+// form for: not causal, Sq == Sk, Hk == H, S in kFusedBwd; everything else runs the split kernels
+// whatever the switch says.
+TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                              long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
+                              const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk, long long lddk,
+                              bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int Hk, int Sq, int Sk,
+                              float p_drop, const long long* rng, unsigned site, int causal, hipStream_t st) {
+  if (!args_ok(H, Hk, Sq, Sk, causal, p_drop, rng, ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv,
+               {q, k, v, o, dout}))
     return hipErrorInvalidValue;
-  const int S = Sq;
+  const bool gqa = Hk != H, drop = p_drop > 0.f;
   AttnParams P = make_params(B, H, Hk, Sq, Sk, seqlen, p_drop, rng, site);
   P.q = q; P.k = k; P.v = v; P.o = o; P.dout = dout;
   P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo; P.lddo = lddo;
   P.lse = const_cast<float*>(lse);
   P.delta = delta;
-  if (!causal && Sq == Sk && Hk == H && attn_fused_bwd() && (S == 128 || S == 256 || S == 512)) {
-    // one workgroup per (batch, head): dQ, dK, dV in one pass (attn_bwd_fused_kernel)
-    P.out = dq; P.ld_out = lddq; P.out2 = dk; P.ld_out2 = lddk; P.out3 = dv; P.ld_out3 = lddv;
-    const dim3 g1(B * H);
-    const bool d = p_drop > 0.f;
-    // S = 512: 8 waves x 64 keys (two waves per SIMD); S = 256 / 128: 4 waves x 64 / 32 keys
-    if (S == 512) {
-      if (d) hipLaunchKernelGGL((attn_bwd_fused_kernel<4, 8, true>), g1, dim3(512), 0, st, P);
-      else hipLaunchKernelGGL((attn_bwd_fused_kernel<4, 8, false>), g1, dim3(512), 0, st, P);
-    } else if (S == 256) {
-      if (d) hipLaunchKernelGGL((attn_bwd_fused_kernel<4, 4, true>), g1, dim3(256), 0, st, P);
-      else hipLaunchKernelGGL((attn_bwd_fused_kernel<4, 4, false>), g1, dim3(256), 0, st, P);
-    } else {
-      if (d) hipLaunchKernelGGL((attn_bwd_fused_kernel<2, 4, true>), g1, dim3(256), 0, st, P);
-      else hipLaunchKernelGGL((attn_bwd_fused_kernel<2, 4, false>), g1, dim3(256), 0, st, P);
+  if (!causal && Sq == Sk && !gqa && attn_fused_bwd()) {
+    for (const FusedBwd& f : kFusedBwd) {
+      if (f.S != Sq) continue;
+      P.out = dq; P.ld_out = lddq; P.out2 = dk; P.ld_out2 = lddk; P.out3 = dv; P.ld_out3 = lddv;
+      hipLaunchKernelGGL(f.kernel[drop], dim3(B * H), dim3(f.threads), 0, st, P);
+      return hipGetLastError();
     }
-    return hipGetLastError();
   }
-  // bwd_q owns query blocks of the H query heads, bwd_kv key blocks of the Hk key/value heads: two
-  // grid sizes when Sq != Sk or Hk != H
-  dim3 grid(B * H * (Sq / QBLK)), grid_kv(B * Hk * (Sk / QBLK)), block(256);
+  if (causal) P.order = causal_order();
   // dQ first: it computes delta (rowsum dO . O) on the way and stores it for dK / dV
   P.out = dq; P.ld_out = lddq; P.out2 = nullptr;
-  if (causal) {
-    P.order = causal_order();
-    if (Hk != H) {
-      if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_q_kernel<true, true, true>), grid, block, 0, st, P);
-      else hipLaunchKernelGGL((attn_bwd_q_kernel<false, true, true>), grid, block, 0, st, P);
-    } else if (p_drop > 0.f) {
-      hipLaunchKernelGGL((attn_bwd_q_kernel<true, true>), grid, block, 0, st, P);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_q_kernel<false, true>), grid, block, 0, st, P);
-    }
-    P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
-    if (Hk != H) {
-      if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, true, true>), grid_kv, block, 0, st, P);
-      else hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, true, true>), grid_kv, block, 0, st, P);
-    } else if (p_drop > 0.f) {
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, true>), grid_kv, block, 0, st, P);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, true>), grid_kv, block, 0, st, P);
-    }
-    return hipGetLastError();
-  }
-  if (Hk != H) {
-    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_q_kernel<true, false, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_bwd_q_kernel<false, false, true>), grid, block, 0, st, P);
-  } else if (p_drop > 0.f) {
-    hipLaunchKernelGGL(attn_bwd_q_kernel<true>, grid, block, 0, st, P);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_q_kernel<false>, grid, block, 0, st, P);
-  }
+  hipLaunchKernelGGL(kBwdQ[gqa][causal != 0][drop], dim3(B * H * (Sq / QBLK)), dim3(256), 0, st, P);
   P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
-  if (Hk != H) {  // the grouped form; the diagnostic forms below are self-attention kernels
-    if (p_drop > 0.f) hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0, false, true>), grid_kv, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_bwd_kv_kernel<false, 0, false, true>), grid_kv, block, 0, st, P);
-    return hipGetLastError();
+  AttnKernel kv = kBwdKv[gqa][causal != 0][drop];
+  if (!gqa && !causal && drop) {
+    for (const KvDiag& d : kKvDiag)
+      if (d.mode == kv_diag()) kv = d.kernel;
   }
-  static const int kv_diag = [] {
-    const char* e = getenv("TTD_ATTN_KV_DIAG");
-    return e ? atoi(e) : 0;
-  }();
-  if (p_drop > 0.f) {
-    switch (kv_diag) {
-      case 1: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 1>), grid_kv, block, 0, st, P); break;
-      case 2: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 2>), grid_kv, block, 0, st, P); break;
-      case 6: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 6>), grid_kv, block, 0, st, P); break;
-      case 7: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 7>), grid_kv, block, 0, st, P); break;
-      case 8: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 8>), grid_kv, block, 0, st, P); break;
-      case 15: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 15>), grid_kv, block, 0, st, P); break;
-      default: hipLaunchKernelGGL((attn_bwd_kv_kernel<true, 0>), grid_kv, block, 0, st, P);
-    }
-  } else {
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid_kv, block, 0, st, P);
-  }
+  hipLaunchKernelGGL(kv, dim3(B * Hk * (Sk / QBLK)), dim3(256), 0, st, P);
   return hipGetLastError();
-}
-
-TTDK_EXPORT int ttdk_attn_bwd_cross(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                    long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
-                                    long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
-                                    bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
-                                    int H, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
-                                    int causal, hipStream_t st) {
-  return ttdk_attn_bwd_gqa(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv,
-                           seqlen, B, H, H, Sq, Sk, p_drop, rng, site, causal, st);
-}
-
-TTDK_EXPORT int ttdk_attn_bwd_causal(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                                     long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout,
-                                     long long lddo, const float* lse, float* delta, bf16_t* dq, long long lddq,
-                                     bf16_t* dk, long long lddk, bf16_t* dv, long long lddv, const int* seqlen, int B,
-                                     int H, int S, float p_drop, const long long* rng, unsigned site, int causal,
-                                     hipStream_t st) {
-  return ttdk_attn_bwd_cross(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv,
-                             seqlen, B, H, S, S, p_drop, rng, site, causal, st);
-}
-
-TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
-                              long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
-                              const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk, long long lddk,
-                              bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int S, float p_drop,
-                              const long long* rng, unsigned site, hipStream_t st) {
-  return ttdk_attn_bwd_causal(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv,
-                              seqlen, B, H, S, p_drop, rng, site, 0, st);
 }

@@ -12,14 +12,8 @@ from . import _lib
 from ._lib import F, I, L, P
 
 _lib.register({
-    "ttdk_attn_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, F, P, I, P],
-    "ttdk_attn_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, P],
-    "ttdk_attn_fwd_causal": [P, L, P, L, P, L, P, L, P, P, I, I, I, F, P, I, I, P],
-    "ttdk_attn_bwd_causal": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, F, P, I, I, P],
-    "ttdk_attn_fwd_cross": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, F, P, I, I, P],
-    "ttdk_attn_bwd_cross": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, F, P, I, I, P],
-    "ttdk_attn_fwd_gqa": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, I, P],
-    "ttdk_attn_bwd_gqa": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, I, P],
+    "ttdk_attn_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, I, P],
+    "ttdk_attn_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, I, P],
     "ttdk_attn_set_fused_bwd": [I],
     "ttdk_ln_fwd": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
     "ttdk_ln_bwd_num_blocks": [I],
@@ -75,19 +69,10 @@ def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, 
     Hk (None: H) is the number of key/value heads — grouped-query attention (Hk == 1: multi-query):
     H % Hk == 0 and query head h reads key/value head h // (H // Hk), the layout of
     repeat_interleave over the head axis."""
-    if Hk is not None and Hk != H:
-        _lib.call("ttdk_attn_fwd_gqa", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, int(Hk), S,
-                  int(S if Sk is None else Sk), float(p_drop), _p(rng.t if rng is not None else None), int(site),
-                  int(bool(causal)), _s())
-    elif Sk is None or Sk == S:
-        _lib.call("ttdk_attn_fwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, float(p_drop),
-                  _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
-    else:
-        _lib.call("ttdk_attn_fwd_cross", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, S, int(Sk),
-                  float(p_drop), _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
+    _lib.call("ttdk_attn_fwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+              out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, int(H if Hk is None else Hk), S,
+              int(S if Sk is None else Sk), float(p_drop), _p(rng.t if rng is not None else None), int(site),
+              int(bool(causal)), _s())
     return out, lse
 
 
@@ -109,24 +94,11 @@ def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=Non
     registers in head order (deterministic), rounded to bf16 once."""
     if delta is None:
         delta = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
-    if Hk is not None and Hk != H:
-        _lib.call("ttdk_attn_bwd_gqa", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
-                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
-                  dv.stride(0), _p(seqlen), B, H, int(Hk), S, int(S if Sk is None else Sk), float(p_drop),
-                  _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
-    elif Sk is None or Sk == S:
-        _lib.call("ttdk_attn_bwd_causal", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
-                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
-                  dv.stride(0), _p(seqlen), B, H, S, float(p_drop), _p(rng.t if rng is not None else None),
-                  int(site), int(bool(causal)), _s())
-    else:
-        _lib.call("ttdk_attn_bwd_cross", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
-                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
-                  dv.stride(0), _p(seqlen), B, H, S, int(Sk), float(p_drop),
-                  _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
+    _lib.call("ttdk_attn_bwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+              o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(), delta.data_ptr(),
+              dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), _p(seqlen),
+              B, H, int(H if Hk is None else Hk), S, int(S if Sk is None else Sk), float(p_drop),
+              _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
     return dq, dk, dv
 
 

@@ -1,41 +1,19 @@
 """Causal (left-to-right) attention: the `causal` flag of the flash kernels, of `ttd.nn.attention`
 (GPU kernels and CPU path), `layers.MultiHeadAttention(use_causal_mask=True)` and the BERT engine
 (`BertConfig.causal`). The kernels are checked against the fp32 autograd oracle of
-tests/test_kernels_transformer.py with a triangular mask added, and for exactness: a masked key
+tests/attention_oracle.py with its triangular mask, and for exactness: a masked key
 contributes exact zeros, so outputs and gradients of positions <= t do not change by one bit
 when keys / values after t do."""
-import math
-
 import pytest
 import torch
 
+from attention_oracle import ref as _ref, run_case
 from tensorflow_train_distributed_amd import layers as L
 from tensorflow_train_distributed_amd import nn as N
 from tensorflow_train_distributed_amd.models.bert import BertConfig, BertPretraining, synthetic_batch
 from tensorflow_train_distributed_amd.ops import transformer as T
 
 gpu = pytest.mark.gpu
-
-
-def _scores(q, k, B, H, S, seqlen, causal):
-    """[B, H, S, S] fp32 scores of token-major [B*S, H*64] q / k, masked keys at -inf."""
-    qh = q.view(B, S, H, 64).transpose(1, 2)
-    kh = k.view(B, S, H, 64).transpose(1, 2)
-    sc = qh @ kh.transpose(-1, -2) / 8.0
-    if seqlen is not None:
-        ar = torch.arange(S, device=q.device)
-        sc = sc.masked_fill(~(ar[None, :] < seqlen[:, None].long())[:, None, None, :], float("-inf"))
-    if causal:
-        tri = torch.ones(S, S, dtype=torch.bool, device=q.device).tril()
-        sc = sc.masked_fill(~tri, float("-inf"))
-    return sc
-
-
-def _ref(q, k, v, B, H, S, seqlen=None, causal=True, keep=None, p=0.0):
-    pr = _scores(q, k, B, H, S, seqlen, causal).softmax(-1)
-    if keep is not None:
-        pr = pr * keep * T.attention_drop_scale(p)
-    return (pr @ v.view(B, S, H, 64).transpose(1, 2)).transpose(1, 2).reshape(B * S, H * 64)
 
 
 # ------------------------------------------------------------------ CPU
@@ -49,7 +27,8 @@ def test_nn_attention_causal_cpu_matches_masked_softmax(masked):
     do = torch.randn_like(o)
     o.backward(do)
     qr, kr, vr = [t.detach().clone().requires_grad_(True) for t in (q, k, v)]
-    ref = _ref(qr.view(B * S, -1), kr.view(B * S, -1), vr.view(B * S, -1), B, H, S, seqlen).view(B, S, -1)
+    ref = _ref(qr.view(B * S, -1), kr.view(B * S, -1), vr.view(B * S, -1), B, H, H, S, S, seqlen,
+               True).view(B, S, -1)
     ref.backward(do)
     torch.testing.assert_close(o, ref, atol=1e-5, rtol=1e-5)
     for a, b in ((q, qr), (k, kr), (v, vr)):
@@ -75,46 +54,6 @@ def test_multi_head_attention_use_causal_mask_cpu():
 
 
 # ------------------------------------------------------------------ GPU kernels vs fp32 oracle
-def _run_case(S, seqlen, p, fused=False):
-    torch.manual_seed(0)
-    B, H = 2, 3
-    D = H * 64
-    dev = "cuda"
-    qkv = (torch.randn(B * S, 3 * D, device=dev) * 1.5).bfloat16()
-    q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
-    seqlen = torch.tensor(seqlen, dtype=torch.int32, device=dev) if seqlen is not None else None
-    rng = T.RngState(99, dev) if p > 0 else None
-    if rng is not None:
-        rng.advance()
-    o = torch.empty(B * S, D, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * H, S, dtype=torch.float32, device=dev)
-    T.attention_fwd(q, k, v, o, lse, B, H, S, seqlen=seqlen, p_drop=p, rng=rng, site=5, causal=True)
-    keep = None
-    if p > 0:
-        seed, step = rng.host()
-        # the unchanged host mirror of the absolute-index hash; the triangle zeroes the rest
-        keep = torch.from_numpy(T.attention_keep_mask(seed, step, 5, p, B, H, S)).float().to(dev)
-        keep = keep * torch.ones(S, S, device=dev).tril()
-    qf, kf, vf = [t.float().requires_grad_(True) for t in (q, k, v)]
-    ref = _ref(qf, kf, vf, B, H, S, seqlen, True, keep, p)
-    torch.testing.assert_close(o.float(), ref, atol=3e-2, rtol=3e-2)
-    lse_ref = torch.logsumexp(_scores(qf, kf, B, H, S, seqlen, True), -1).reshape(B * H, S) / math.log(2)
-    torch.testing.assert_close(lse, lse_ref.detach(), atol=2e-2, rtol=1e-3)
-    do = torch.randn(B * S, D, device=dev).bfloat16()
-    ref.backward(do.float())
-    dqkv = torch.empty_like(qkv)
-    T.set_fused_attention_bwd(fused)
-    try:
-        T.attention_bwd(q, k, v, o, do, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:], B, H, S, seqlen=seqlen,
-                        p_drop=p, rng=rng, site=5, causal=True)
-    finally:
-        T.set_fused_attention_bwd(False)
-    for name, got, want in (("dq", dqkv[:, :D], qf.grad), ("dk", dqkv[:, D:2 * D], kf.grad),
-                            ("dv", dqkv[:, 2 * D:], vf.grad)):
-        rel = float((got.float() - want).norm() / want.norm())
-        assert rel < 2e-2, (name, rel)
-
-
 @gpu
 @pytest.mark.parametrize("S,seqlen,p", [
     (128, None, 0.0),         # one block: diagonal tiles only
@@ -123,14 +62,14 @@ def _run_case(S, seqlen, p, fused=False):
     (256, [256, 37], 0.0),    # len inside the first tile: query rows >= len see only keys < len
 ])
 def test_causal_attention_fwd_bwd_matches_reference(S, seqlen, p):
-    _run_case(S, seqlen, p)
+    run_case(3, 3, S, S, True, seqlen, p, fused_layout=True)
 
 
 @gpu
 def test_causal_backward_ignores_fused_switch():
     """The fused single-kernel backward has no causal form: with the switch on, a causal
     backward still runs the split kernels and meets the same bars."""
-    _run_case(256, None, 0.1, fused=True)
+    run_case(3, 3, 256, 256, True, None, 0.1, fused=True, fused_layout=True)
 
 
 # ------------------------------------------------------------------ exactness on the GPU

@@ -1,47 +1,25 @@
 """Cross-attention: a key length `Sk` apart from the query length in the flash kernels
-(`ttdk_attn_fwd_cross` / `ttdk_attn_bwd_cross`), `ops.transformer.attention_fwd / _bwd(Sk=)`,
+(`ttdk_attn_fwd` / `ttdk_attn_bwd` with Sk != Sq), `ops.transformer.attention_fwd / _bwd(Sk=)`,
 `attention_keep_mask(Sk=)`, `ttd.nn.attention` with k / v of another length (GPU kernels and CPU
 path) and `layers.MultiHeadAttention(x, value=mem)`.
 
-The kernels are checked against the fp32 autograd oracle of tests/test_attention_causal.py with
-separate query and key lengths, at that file's bars (o: atol = rtol = 3e-2; lse: atol 2e-2, rtol
+The kernels are checked against the fp32 autograd oracle of tests/attention_oracle.py with
+separate query and key lengths, at its bars (o: atol = rtol = 3e-2; lse: atol 2e-2, rtol
 1e-3; dq / dk / dv: relative L2 error < 2e-2), and for exactness: keys past the memory's length
-add exact zeros, query blocks do not see each other, and the new entry at Sk == S is the existing
-entry bit for bit."""
+add exact zeros, query blocks do not see each other, and the general argument list at Sk == S
+gives the self-attention bits."""
 import math
 
 import pytest
 import torch
 
+from attention_oracle import assert_explicit_entry_is_self_attention, ref as _ref, rel as _rel, run_case
 from tensorflow_train_distributed_amd import layers as L
 from tensorflow_train_distributed_amd import nn as N
 from tensorflow_train_distributed_amd.ops import transformer as T
 from tensorflow_train_distributed_amd.utils.errors import InvalidArgumentError
 
 gpu = pytest.mark.gpu
-
-
-def _scores(q, k, B, H, Sq, Sk, seqlen):
-    """[B, H, Sq, Sk] fp32 scores of token-major q [B*Sq, H*64] and k [B*Sk, H*64]; keys >=
-    seqlen[b] at -inf."""
-    qh = q.reshape(B, Sq, H, 64).transpose(1, 2)
-    kh = k.reshape(B, Sk, H, 64).transpose(1, 2)
-    sc = qh @ kh.transpose(-1, -2) / 8.0
-    if seqlen is not None:
-        ar = torch.arange(Sk, device=q.device)
-        sc = sc.masked_fill(~(ar[None, :] < seqlen[:, None].long())[:, None, None, :], float("-inf"))
-    return sc
-
-
-def _ref(q, k, v, B, H, Sq, Sk, seqlen=None, keep=None, p=0.0):
-    pr = _scores(q, k, B, H, Sq, Sk, seqlen).softmax(-1)
-    if keep is not None:
-        pr = pr * keep * T.attention_drop_scale(p)
-    return (pr @ v.reshape(B, Sk, H, 64).transpose(1, 2)).transpose(1, 2).reshape(B * Sq, H * 64)
-
-
-def _rel(got, want):
-    return float((got.float() - want.float()).norm() / want.float().norm())
 
 
 # ------------------------------------------------------------------ CPU
@@ -57,7 +35,7 @@ def test_nn_attention_cross_cpu_matches_masked_softmax(Sq, Sk, seqlen):
     do = torch.randn_like(o)
     o.backward(do)
     qr, kr, vr = [t.detach().clone().requires_grad_(True) for t in (q, k, v)]
-    ref = _ref(qr.view(B * Sq, -1), kr.view(B * Sk, -1), vr.view(B * Sk, -1), B, H, Sq, Sk, seqlen).view(B, Sq, -1)
+    ref = _ref(qr.view(B * Sq, -1), kr.view(B * Sk, -1), vr.view(B * Sk, -1), B, H, H, Sq, Sk, seqlen).view(B, Sq, -1)
     ref.backward(do)
     torch.testing.assert_close(o, ref, atol=1e-5, rtol=1e-5)
     assert k.grad.shape == (B, Sk, H * 64) and v.grad.shape == (B, Sk, H * 64)
@@ -112,7 +90,7 @@ def test_multi_head_attention_value_cpu():
         q = x @ W[:, :inner] + b[:inner]
         k = mem @ W[:, inner:2 * inner] + b[inner:2 * inner]
         v = mem @ W[:, 2 * inner:] + b[2 * inner:]
-        a = _ref(q.reshape(B * S, inner), k.reshape(B * Sk, inner), v.reshape(B * Sk, inner), B, H, S, Sk, seqlen)
+        a = _ref(q.reshape(B * S, inner), k.reshape(B * Sk, inner), v.reshape(B * Sk, inner), B, H, H, S, Sk, seqlen)
         want = a.view(B, S, inner) @ layer.out_kernel + layer.out_bias
         assert y.shape == (B, S, D)
         torch.testing.assert_close(y, want, atol=1e-5, rtol=1e-4)
@@ -123,52 +101,6 @@ def test_multi_head_attention_value_cpu():
 
 
 # ------------------------------------------------------------------ GPU kernels vs fp32 oracle
-def _run_case(Sq, Sk, seqlen, p, fused=False):
-    torch.manual_seed(0)
-    B, H = 2, 3
-    D = H * 64
-    dev = "cuda"
-    q = (torch.randn(B * Sq, D, device=dev) * 1.5).bfloat16()
-    kv = (torch.randn(B * Sk, 2 * D, device=dev) * 1.5).bfloat16()
-    k, v = kv[:, :D], kv[:, D:]  # ldk = ldv = 2 D != ldq
-    seqlen = torch.tensor(seqlen, dtype=torch.int32, device=dev) if seqlen is not None else None
-    rng = T.RngState(99, dev) if p > 0 else None
-    if rng is not None:
-        rng.advance()
-    o = torch.empty(B * Sq, D, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * H, Sq, dtype=torch.float32, device=dev)
-    T.attention_fwd(q, k, v, o, lse, B, H, Sq, Sk=Sk, seqlen=seqlen, p_drop=p, rng=rng, site=5)
-    keep = None
-    if p > 0:
-        seed, step = rng.host()
-        keep = torch.from_numpy(T.attention_keep_mask(seed, step, 5, p, B, H, Sq, Sk)).float().to(dev)
-    qf, kf, vf = [t.float().requires_grad_(True) for t in (q, k, v)]
-    ref = _ref(qf, kf, vf, B, H, Sq, Sk, seqlen, keep, p)
-    print("o max abs err", float((o.float() - ref.detach()).abs().max()))
-    torch.testing.assert_close(o.float(), ref, atol=3e-2, rtol=3e-2)
-    lse_ref = torch.logsumexp(_scores(qf, kf, B, H, Sq, Sk, seqlen), -1).reshape(B * H, Sq) / math.log(2)
-    print("lse max abs err", float((lse - lse_ref.detach()).abs().max()))
-    torch.testing.assert_close(lse, lse_ref.detach(), atol=2e-2, rtol=1e-3)
-    do = torch.randn(B * Sq, D, device=dev).bfloat16()
-    ref.backward(do.float())
-    dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv)
-    T.set_fused_attention_bwd(fused)
-    try:
-        T.attention_bwd(q, k, v, o, do, lse, dq, dkv[:, :D], dkv[:, D:], B, H, Sq, Sk=Sk, seqlen=seqlen, p_drop=p,
-                        rng=rng, site=5)
-    finally:
-        T.set_fused_attention_bwd(False)
-    rels = [(name, _rel(got, want)) for name, got, want in
-            (("dq", dq, qf.grad), ("dk", dkv[:, :D], kf.grad), ("dv", dkv[:, D:], vf.grad))]
-    print("rel L2", rels)
-    for name, rel in rels:
-        assert rel < 2e-2, (name, rel)
-    if seqlen is not None:  # keys >= len: exact zeros, not small numbers
-        dead = (torch.arange(B * Sk, device=dev) % Sk) >= seqlen.long().repeat_interleave(Sk)
-        assert bool(dead.any()) and float(dkv[dead].float().abs().max()) == 0.0
-
-
 @gpu
 @pytest.mark.parametrize("Sq,Sk,seqlen,p", [
     (128, 256, None, 0.0),          # more key blocks than query blocks: bwd_kv's grid is the larger
@@ -177,20 +109,20 @@ def _run_case(Sq, Sk, seqlen, p, fused=False):
     (384, 128, [37, 128], 0.0),     # odd query-block count; len inside the first tile
 ])
 def test_cross_attention_fwd_bwd_matches_reference(Sq, Sk, seqlen, p):
-    _run_case(Sq, Sk, seqlen, p)
+    run_case(3, 3, Sq, Sk, False, seqlen, p)
 
 
 @gpu
 def test_cross_backward_ignores_fused_switch():
     """The fused single-kernel backward is a self-attention kernel: with the switch on, a backward
     with Sq != Sk still runs the split kernels and meets the same bars."""
-    _run_case(256, 128, None, 0.1, fused=True)
+    run_case(3, 3, 256, 128, False, None, 0.1, fused=True)
 
 
 # ------------------------------------------------------------------ exactness on the GPU
 def _run(q, k, v, do, B, H, Sq, Sk, *, seqlen=None, p=0.0, rng=None, site=2, cross=True):
     """Forward + split backward into fresh buffers; cross=False goes through the call without Sk
-    (the existing entry points)."""
+    (the wrapper fills in Sk = Sq)."""
     D = H * 64
     dev = q.device
     o = torch.empty(B * Sq, D, dtype=torch.bfloat16, device=dev)
@@ -251,28 +183,11 @@ def test_query_blocks_are_independent():
 
 @gpu
 def test_cross_entry_equals_self_entry_at_equal_lengths():
-    torch.manual_seed(5)
-    B, H, S, p = 2, 3, 256, 0.1
-    D = H * 64
-    dev = "cuda"
-    q, k, v, do = [(torch.randn(B * S, D, device=dev) * 1.5).bfloat16() for _ in range(4)]
-    rng = T.RngState(11, dev)
-    seqlen = torch.tensor([S, 150], dtype=torch.int32, device=dev)
-    want = _run(q, k, v, do, B, H, S, S, seqlen=seqlen, p=p, rng=rng, cross=False)
-    # straight at the new symbols (attention_fwd / _bwd route Sk == S to the existing ones)
-    o = torch.empty_like(want[0])
-    lse = torch.empty_like(want[1])
-    dq, dk, dv = [torch.empty_like(t) for t in want[2:]]
-    delta = torch.empty_like(lse)
-    st = T._lib.stream()
-    T._lib.call("ttdk_attn_fwd_cross", q.data_ptr(), D, k.data_ptr(), D, v.data_ptr(), D, o.data_ptr(), D,
-                lse.data_ptr(), seqlen.data_ptr(), B, H, S, S, p, rng.t.data_ptr(), 2, 0, st)
-    T._lib.call("ttdk_attn_bwd_cross", q.data_ptr(), D, k.data_ptr(), D, v.data_ptr(), D, o.data_ptr(), D,
-                do.data_ptr(), D, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), D, dk.data_ptr(), D,
-                dv.data_ptr(), D, seqlen.data_ptr(), B, H, S, S, p, rng.t.data_ptr(), 2, 0, st)
-    for name, a, b in zip(("o", "lse", "dq", "dk", "dv"), (o, lse, dq, dk, dv), want):
-        assert torch.equal(a, b), name
-    assert float(dq.float().abs().max()) > 0
+    """One entry pair takes Sq and Sk, so there is no second symbol to compare with: the general
+    argument list at Sk == Sq must give the bits of the wrapper call without Sk, and the bits the
+    self-attention entry points gave before the merge (tests/golden/attention_parent_bits.json)."""
+    for cid in ("self-p0.1-full", "self-p0.1-causal"):
+        assert_explicit_entry_is_self_attention(cid)
 
 
 @gpu

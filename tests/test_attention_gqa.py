@@ -1,55 +1,27 @@
 """Grouped-query attention (GQA; one key/value head: multi-query attention): H query heads over
-Hk < H key/value heads in the flash kernels (`ttdk_attn_fwd_gqa` / `ttdk_attn_bwd_gqa`),
+Hk < H key/value heads in the flash kernels (`ttdk_attn_fwd` / `ttdk_attn_bwd` with Hk != H),
 `ops.transformer.attention_fwd / _bwd(Hk=)`, `ttd.nn.attention(num_kv_heads=)` (GPU kernels and
 CPU path) and `layers.MultiHeadAttention(num_kv_heads=)`. Query head h uses key/value head
 h // (H // Hk): the layout of `repeat_interleave` over the head axis.
 
-The kernels are checked against the fp32 autograd oracle of tests/test_attention_causal.py and
-tests/test_attention_cross.py with the key/value heads repeated explicitly, at those files' bars
+The kernels are checked against the fp32 autograd oracle of tests/attention_oracle.py, which
+repeats the key/value heads explicitly, at its bars
 (o: atol = rtol = 3e-2; lse: atol 2e-2, rtol 1e-3; dq / dk / dv: relative L2 error < 2e-2), and
-for exactness: o, lse and dq equal a self-attention run over repeated heads bit for bit, the new
-entry at Hk == H is the existing entry bit for bit, groups do not see each other, and dk / dv
-(summed over a group's heads in registers, in head order) are deterministic."""
+for exactness: o, lse and dq equal a self-attention run over repeated heads bit for bit, the
+general argument list at Hk == H gives the self-attention bits, groups do not see each other, and
+dk / dv (summed over a group's heads in registers, in head order) are deterministic."""
 import math
 
 import pytest
 import torch
 
+from attention_oracle import assert_explicit_entry_is_self_attention, ref as _ref, rel as _rel, run_case
 from tensorflow_train_distributed_amd import layers as L
 from tensorflow_train_distributed_amd import nn as N
 from tensorflow_train_distributed_amd.ops import transformer as T
 from tensorflow_train_distributed_amd.utils.errors import InvalidArgumentError
 
 gpu = pytest.mark.gpu
-
-
-def _heads(t, B, S, Hk, H):
-    """[B, H, S, 64] of token-major t [B*S, Hk*64], each key/value head repeated H // Hk times."""
-    return t.reshape(B, S, Hk, 64).transpose(1, 2).repeat_interleave(H // Hk, dim=1)
-
-
-def _scores(q, k, B, H, Hk, Sq, Sk, seqlen, causal):
-    """[B, H, Sq, Sk] fp32 scores of token-major q [B*Sq, H*64] and k [B*Sk, Hk*64]; masked keys
-    at -inf."""
-    sc = _heads(q, B, Sq, H, H) @ _heads(k, B, Sk, Hk, H).transpose(-1, -2) / 8.0
-    if seqlen is not None:
-        ar = torch.arange(Sk, device=q.device)
-        sc = sc.masked_fill(~(ar[None, :] < seqlen[:, None].long())[:, None, None, :], float("-inf"))
-    if causal:
-        tri = torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).tril()
-        sc = sc.masked_fill(~tri, float("-inf"))
-    return sc
-
-
-def _ref(q, k, v, B, H, Hk, Sq, Sk, seqlen=None, causal=False, keep=None, p=0.0):
-    pr = _scores(q, k, B, H, Hk, Sq, Sk, seqlen, causal).softmax(-1)
-    if keep is not None:
-        pr = pr * keep * T.attention_drop_scale(p)
-    return (pr @ _heads(v, B, Sk, Hk, H)).transpose(1, 2).reshape(B * Sq, H * 64)
-
-
-def _rel(got, want):
-    return float((got.float() - want.float()).norm() / want.float().norm())
 
 
 # ------------------------------------------------------------------ CPU
@@ -152,53 +124,6 @@ def test_multi_head_attention_num_kv_heads_cpu():
 
 
 # ------------------------------------------------------------------ GPU kernels vs fp32 oracle
-def _run_case(H, Hk, Sq, Sk, causal, seqlen, p, fused=False):
-    torch.manual_seed(0)
-    B = 2
-    D, Dk = H * 64, Hk * 64
-    dev = "cuda"
-    q = (torch.randn(B * Sq, D, device=dev) * 1.5).bfloat16()
-    kv = (torch.randn(B * Sk, 2 * Dk, device=dev) * 1.5).bfloat16()
-    k, v = kv[:, :Dk], kv[:, Dk:]  # ldk = ldv = 2 Dk != ldq
-    seqlen = torch.tensor(seqlen, dtype=torch.int32, device=dev) if seqlen is not None else None
-    rng = T.RngState(99, dev) if p > 0 else None
-    if rng is not None:
-        rng.advance()
-    o = torch.empty(B * Sq, D, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * H, Sq, dtype=torch.float32, device=dev)
-    kw = dict(Sk=Sk, Hk=Hk, seqlen=seqlen, p_drop=p, rng=rng, site=5, causal=causal)
-    T.attention_fwd(q, k, v, o, lse, B, H, Sq, **kw)
-    keep = None
-    if p > 0:
-        seed, step = rng.host()
-        # per query head: H masks, not Hk
-        keep = torch.from_numpy(T.attention_keep_mask(seed, step, 5, p, B, H, Sq, Sk)).float().to(dev)
-    qf, kf, vf = [t.float().requires_grad_(True) for t in (q, k, v)]
-    ref = _ref(qf, kf, vf, B, H, Hk, Sq, Sk, seqlen, causal, keep, p)
-    print("o max abs err", float((o.float() - ref.detach()).abs().max()))
-    torch.testing.assert_close(o.float(), ref, atol=3e-2, rtol=3e-2)
-    lse_ref = torch.logsumexp(_scores(qf, kf, B, H, Hk, Sq, Sk, seqlen, causal), -1).reshape(B * H, Sq) / math.log(2)
-    print("lse max abs err", float((lse - lse_ref.detach()).abs().max()))
-    torch.testing.assert_close(lse, lse_ref.detach(), atol=2e-2, rtol=1e-3)
-    do = torch.randn(B * Sq, D, device=dev).bfloat16()
-    ref.backward(do.float())
-    dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv)
-    T.set_fused_attention_bwd(fused)
-    try:
-        T.attention_bwd(q, k, v, o, do, lse, dq, dkv[:, :Dk], dkv[:, Dk:], B, H, Sq, **kw)
-    finally:
-        T.set_fused_attention_bwd(False)
-    rels = [(name, _rel(got, want)) for name, got, want in
-            (("dq", dq, qf.grad), ("dk", dkv[:, :Dk], kf.grad), ("dv", dkv[:, Dk:], vf.grad))]
-    print("rel L2", rels)
-    for name, rel in rels:
-        assert rel < 2e-2, (name, rel)
-    if seqlen is not None:  # keys >= len: exact zeros, not small numbers
-        dead = (torch.arange(B * Sk, device=dev) % Sk) >= seqlen.long().repeat_interleave(Sk)
-        assert bool(dead.any()) and float(dkv[dead].float().abs().max()) == 0.0
-
-
 @gpu
 @pytest.mark.parametrize("H,Hk,Sq,Sk,causal,seqlen,p", [
     # two groups; two query blocks, so a group's second head reads lse / delta rows at another bh*S
@@ -211,20 +136,20 @@ def _run_case(H, Hk, Sq, Sk, causal, seqlen, p, fused=False):
     (4, 2, 256, 256, True, None, 0.0),
 ])
 def test_gqa_fwd_bwd_matches_reference(H, Hk, Sq, Sk, causal, seqlen, p):
-    _run_case(H, Hk, Sq, Sk, causal, seqlen, p)
+    run_case(H, Hk, Sq, Sk, causal, seqlen, p)
 
 
 @gpu
 def test_gqa_backward_ignores_fused_switch():
     """The fused single-kernel backward is an Hk == H kernel: with the switch on, a grouped
     backward still runs the split kernels and meets the same bars."""
-    _run_case(4, 2, 256, 256, False, None, 0.1, fused=True)
+    run_case(4, 2, 256, 256, False, None, 0.1, fused=True)
 
 
 # ------------------------------------------------------------------ exactness on the GPU
 def _run(q, k, v, do, B, H, S, *, Hk=None, seqlen=None, p=0.0, rng=None, site=2, causal=False):
     """Forward + split backward into fresh buffers; Hk=None goes through the call without Hk (the
-    existing entry points)."""
+    wrapper fills in Hk = H)."""
     dev = q.device
     o = torch.empty(B * S, H * 64, dtype=torch.bfloat16, device=dev)
     lse = torch.empty(B * H, S, dtype=torch.float32, device=dev)
@@ -272,28 +197,11 @@ def test_gqa_equals_repeated_heads_bitwise(causal):
 
 @gpu
 def test_gqa_entry_equals_self_entry_at_equal_heads():
-    torch.manual_seed(5)
-    B, H, S, p = 2, 3, 256, 0.1
-    D = H * 64
-    dev = "cuda"
-    q, k, v, do = [(torch.randn(B * S, D, device=dev) * 1.5).bfloat16() for _ in range(4)]
-    rng = T.RngState(11, dev)
-    seqlen = torch.tensor([S, 150], dtype=torch.int32, device=dev)
-    want = _run(q, k, v, do, B, H, S, seqlen=seqlen, p=p, rng=rng)
-    # straight at the new symbols (attention_fwd / _bwd route Hk == H to the existing ones)
-    o = torch.empty_like(want[0])
-    lse = torch.empty_like(want[1])
-    dq, dk, dv = [torch.empty_like(t) for t in want[2:]]
-    delta = torch.empty_like(lse)
-    st = T._lib.stream()
-    T._lib.call("ttdk_attn_fwd_gqa", q.data_ptr(), D, k.data_ptr(), D, v.data_ptr(), D, o.data_ptr(), D,
-                lse.data_ptr(), seqlen.data_ptr(), B, H, H, S, S, p, rng.t.data_ptr(), 2, 0, st)
-    T._lib.call("ttdk_attn_bwd_gqa", q.data_ptr(), D, k.data_ptr(), D, v.data_ptr(), D, o.data_ptr(), D,
-                do.data_ptr(), D, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), D, dk.data_ptr(), D,
-                dv.data_ptr(), D, seqlen.data_ptr(), B, H, H, S, S, p, rng.t.data_ptr(), 2, 0, st)
-    for name, a, b in zip(("o", "lse", "dq", "dk", "dv"), (o, lse, dq, dk, dv), want):
-        assert torch.equal(a, b), name
-    assert float(dk.float().abs().max()) > 0
+    """One entry pair takes Hk, so there is no second symbol to compare with: the general argument
+    list at Hk == H must give the bits of the wrapper call without Hk, and the bits the
+    self-attention entry points gave before the merge (tests/golden/attention_parent_bits.json)."""
+    for cid in ("self-p0.1-full", "self-p0.1-causal"):
+        assert_explicit_entry_is_self_attention(cid)
 
 
 @gpu

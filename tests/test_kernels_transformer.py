@@ -1,12 +1,11 @@
 """Transformer kernels (attention.hip, transformer.hip, GEMM GELU/tanh epilogues) vs plain
 PyTorch fp32 references of the same ops; dropout masks checked against the CPU mirror of
 the kernels' counter hash."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
+from attention_oracle import run_case
 from tensorflow_train_distributed_amd.ops import transformer as T
 
 gpu = pytest.mark.gpu
@@ -19,27 +18,6 @@ def test_dropout_hash_mirror_statistics():
     keep2 = T.keep_mask(1234, 8, 3, 0.1, idx)  # a new step draws a different mask
     assert (keep != keep2).mean() > 0.1
     assert T.drop_threshold(0.0) == 0 and T.drop_threshold(1.0) == 0xFFFFFFFF
-
-
-def _attn_ref(q, k, v, B, H, S, seqlen=None, keep=None, p=0.0):
-    # q/k/v: [B*S, H*64] fp32
-    def heads(t):
-        return t.view(B, S, H, 64).transpose(1, 2)
-    qh, kh, vh = heads(q), heads(k), heads(v)
-    sc = qh @ kh.transpose(-1, -2) / 8.0
-    if seqlen is not None:
-        ar = torch.arange(S, device=q.device)
-        m = ar[None, :] < seqlen[:, None].long()
-        sc = sc.masked_fill(~m[:, None, None, :], float("-inf"))
-    pr = sc.softmax(-1)
-    if keep is not None:
-        pr = pr * keep * T.attention_drop_scale(p)
-    return (pr @ vh).transpose(1, 2).reshape(B * S, H * 64)
-
-
-def _keep_tensor(rng_state, site, p, B, H, S, device):
-    seed, step = rng_state
-    return torch.from_numpy(T.attention_keep_mask(seed, step, site, p, B, H, S)).float().to(device)
 
 
 def test_attention_dropout_pair_hash_statistics():
@@ -87,44 +65,7 @@ def test_attention_pair_hash_has_full_32_bit_range():
 def test_attention_fwd_bwd_matches_reference(S, masked, p, fused):
     """fp32 autograd oracle; the backward on the single-kernel path (fused, S in {128, 256, 512})
     and on the split dQ / dK-dV kernels."""
-    torch.manual_seed(0)
-    B, H = 2, 3
-    D = H * 64
-    dev = "cuda"
-    qkv = (torch.randn(B * S, 3 * D, device=dev) * 1.5).bfloat16()
-    q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
-    seqlen = torch.tensor([S, S // 2 + 22], dtype=torch.int32, device=dev) if masked else None
-    rng = T.RngState(99, dev) if p > 0 else None
-    if rng is not None:
-        rng.advance()
-    o = torch.empty(B * S, D, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * H, S, dtype=torch.float32, device=dev)
-    T.attention_fwd(q, k, v, o, lse, B, H, S, seqlen=seqlen, p_drop=p, rng=rng, site=5)
-    keep = _keep_tensor(rng.host(), 5, p, B, H, S, dev) if p > 0 else None
-    qf, kf, vf = [t.float().requires_grad_(True) for t in (q, k, v)]
-    ref = _attn_ref(qf, kf, vf, B, H, S, seqlen, keep, p)
-    torch.testing.assert_close(o.float(), ref, atol=3e-2, rtol=3e-2)
-    # lse (log2 domain) vs reference logsumexp
-    sc = (qf.view(B, S, H, 64).transpose(1, 2) @ kf.view(B, S, H, 64).transpose(1, 2).transpose(-1, -2)) / 8.0
-    if masked:
-        ar = torch.arange(S, device=dev)
-        sc = sc.masked_fill(~(ar[None, :] < seqlen[:, None].long())[:, None, None, :], float("-inf"))
-    lse_ref = torch.logsumexp(sc, -1).reshape(B * H, S) / math.log(2)
-    torch.testing.assert_close(lse, lse_ref.detach(), atol=2e-2, rtol=1e-3)
-    # backward
-    do = torch.randn(B * S, D, device=dev).bfloat16()
-    ref.backward(do.float())
-    dqkv = torch.empty_like(qkv)
-    T.set_fused_attention_bwd(fused)
-    try:
-        T.attention_bwd(q, k, v, o, do, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:], B, H, S, seqlen=seqlen,
-                        p_drop=p, rng=rng, site=5)
-    finally:
-        T.set_fused_attention_bwd(False)
-    for name, got, want in (("dq", dqkv[:, :D], qf.grad), ("dk", dqkv[:, D:2 * D], kf.grad),
-                            ("dv", dqkv[:, 2 * D:], vf.grad)):
-        rel = float((got.float() - want).norm() / want.norm())
-        assert rel < 2e-2, (name, rel)
+    run_case(3, 3, S, S, False, [S, S // 2 + 22] if masked else None, p, fused=fused, fused_layout=True)
 
 
 @gpu

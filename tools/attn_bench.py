@@ -49,77 +49,41 @@ if causal and Sk is not None:
 if Hk is not None and Sk is not None:
     sys.exit("--kv-heads and --kv-seq exclude each other")
 B, H, S, D = (int(args[0]) if args else 32), 16, 512, 64
-if Hk is not None:
-    if Hk <= 0 or H % Hk:
-        sys.exit("--kv-heads must divide %d" % H)
-    gqkv = (torch.randn(B * S, (H + 2 * Hk) * D, device="cuda") * 0.5).bfloat16()
-    gq, gk, gv = gqkv[:, :H * D], gqkv[:, H * D:(H + Hk) * D], gqkv[:, (H + Hk) * D:]
-    gd = torch.empty_like(gqkv)
-    gdq, gdk, gdv = gd[:, :H * D], gd[:, H * D:(H + Hk) * D], gd[:, (H + Hk) * D:]
-    gout = torch.empty(B * S, H * D, device="cuda", dtype=torch.bfloat16)
-    glse = torch.empty(B * H, S, device="cuda")
-    gdout = torch.randn_like(gout)
-    grng = T.RngState(7, "cuda")
-    fl_g = 4.0 * B * H * S * S * D
-    T.set_fused_attention_bwd(False)
-    for p in (0.0, 0.1):
-        kw = dict(Hk=Hk, p_drop=p, rng=grng, causal=causal)
-        tf = timeit(lambda: T.attention_fwd(gq, gk, gv, gout, glse, B, H, S, **kw))
-        tb = timeit(lambda: T.attention_bwd(gq, gk, gv, gout, gdout, glse, gdq, gdk, gdv, B, H, S, **kw))
-        print("%skv-heads %2d p=%.1f  fwd %6.1f us %5.0f TF/s   bwd split %6.1f us %5.0f TF/s"
-              % ("causal " if causal else "", Hk, p, tf, fl_g / tf / 1e6, tb, 2.5 * fl_g / tb / 1e6))
-    sys.exit(0)
-qkv = (torch.randn(B * S, 3 * H * D, device="cuda") * 0.5).bfloat16()
-q, k, v = qkv[:, :H * D], qkv[:, H * D:2 * H * D], qkv[:, 2 * H * D:]
+if Hk is not None and (Hk <= 0 or H % Hk):
+    sys.exit("--kv-heads must divide %d" % H)
+# one label, one buffer layout per mode; everything below is shared
+if Sk is not None:
+    label = "cross Sq=%d Sk=%d " % (S, Sk)
+elif Hk is not None:
+    label = "%skv-heads %2d " % ("causal " if causal else "", Hk)
+else:
+    label = "causal " if causal else ""
+Hkv, Skv = H if Hk is None else Hk, S if Sk is None else Sk
+# Q / K / V column views of one fused [B*S, (H + 2*Hkv)*D] projection, dQ / dK / dV of another
+qkv = (torch.randn(B * S, (H + 2 * Hkv) * D, device="cuda") * 0.5).bfloat16()
+dqkv = torch.empty_like(qkv)
+(q, k, v), (dq, dk, dv) = [(t[:, :H * D], t[:, H * D:(H + Hkv) * D], t[:, (H + Hkv) * D:]) for t in (qkv, dqkv)]
 out = torch.empty(B * S, H * D, device="cuda", dtype=torch.bfloat16)
 lse = torch.empty(B * H, S, device="cuda")
+delta = torch.empty_like(lse)
 dout = torch.randn_like(out)
-dqkv = torch.empty_like(qkv)
 rng = T.RngState(7, "cuda")
 if Sk is not None:
     # the memory: K / V out of a fused [B*Sk, 2*H*D] projection, dK / dV into one; Q / dQ stay
-    # views of the [B*S, 3*H*D] buffer. Goes through the cross entry points even at Sk == S.
+    # views of the [B*S, 3*H*D] buffers
     kvm = (torch.randn(B * Sk, 2 * H * D, device="cuda") * 0.5).bfloat16()
-    dkvm = torch.empty_like(kvm)
-    km, vm = kvm[:, :H * D], kvm[:, H * D:]
-    fl_x = 4.0 * B * H * S * Sk * D
-    st = T._lib.stream
-
-    def xfwd(p):
-        T._lib.call("ttdk_attn_fwd_cross", q.data_ptr(), q.stride(0), km.data_ptr(), km.stride(0), vm.data_ptr(),
-                    vm.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), None, B, H, S, Sk, p,
-                    rng.t.data_ptr(), 0, 0, st())
-
-    def xbwd(p):
-        T._lib.call("ttdk_attn_bwd_cross", q.data_ptr(), q.stride(0), km.data_ptr(), km.stride(0), vm.data_ptr(),
-                    vm.stride(0), out.data_ptr(), out.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
-                    delta.data_ptr(), dqkv.data_ptr(), dqkv.stride(0), dkvm.data_ptr(), dkvm.stride(0),
-                    dkvm[:, H * D:].data_ptr(), dkvm.stride(0), None, B, H, S, Sk, p, rng.t.data_ptr(), 0, 0, st())
-
-    delta = torch.empty_like(lse)
-    T.set_fused_attention_bwd(False)
-    for p in (0.0, 0.1):
-        tf = timeit(lambda: xfwd(p))
-        tb = timeit(lambda: xbwd(p))
-        print("cross Sq=%d Sk=%d p=%.1f  fwd %6.1f us %5.0f TF/s   bwd split %6.1f us %5.0f TF/s"
-              % (S, Sk, p, tf, fl_x / tf / 1e6, tb, 2.5 * fl_x / tb / 1e6))
-    sys.exit(0)
-fl_f = 4.0 * B * H * S * S * D
-kw = {"causal": True} if causal else {}
+    (k, v), (dk, dv) = [(t[:, :H * D], t[:, H * D:]) for t in (kvm, torch.empty_like(kvm))]
+# FLOPs 4 B H Sq Sk D; the backward counted as the algorithm's 5 products (2.5x the forward's 2);
+# TF/s of the causal runs are in dense-equivalent FLOPs (the skipped tiles counted), for comparison
+fl = 4.0 * B * H * S * Skv * D
 for p in (0.0, 0.1):
-    tf = timeit(lambda: T.attention_fwd(q, k, v, out, lse, B, H, S, p_drop=p, rng=rng, **kw))
-    res = {}
-    for fused in ((False,) if causal else (True, False)):
+    kw = dict(Sk=Sk, Hk=Hk, p_drop=p, rng=rng, causal=causal)
+    tf = timeit(lambda: T.attention_fwd(q, k, v, out, lse, B, H, S, **kw))
+    line = "%sp=%.1f  fwd %6.1f us %5.0f TF/s   bwd" % (label, p, tf, fl / tf / 1e6)
+    # the fused backward has a self-attention, non-causal form only
+    for fused in ((True, False) if label == "" else (False,)):
         T.set_fused_attention_bwd(fused)
-        res[fused] = timeit(lambda: T.attention_bwd(q, k, v, out, dout, lse, dqkv[:, :H * D], dqkv[:, H * D:2 * H * D],
-                                                    dqkv[:, 2 * H * D:], B, H, S, p_drop=p, rng=rng, **kw))
+        tb = timeit(lambda: T.attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, S, delta=delta, **kw))
+        line += " %s %6.1f us %5.0f TF/s  " % ("fused" if fused else "split", tb, 2.5 * fl / tb / 1e6)
     T.set_fused_attention_bwd(False)
-    # backward FLOPs counted as the algorithm's 5 products (2.5x the forward's 2); TF/s of the
-    # causal runs are in dense-equivalent FLOPs (the skipped tiles counted), for comparison
-    if causal:
-        print("causal p=%.1f  fwd %6.1f us %5.0f TF/s   bwd split %6.1f us %5.0f TF/s"
-              % (p, tf, fl_f / tf / 1e6, res[False], 2.5 * fl_f / res[False] / 1e6))
-    else:
-        print("p=%.1f  fwd %6.1f us %5.0f TF/s   bwd fused %6.1f us %5.0f TF/s   split %6.1f us %5.0f TF/s"
-              % (p, tf, fl_f / tf / 1e6, res[True], 2.5 * fl_f / res[True] / 1e6, res[False],
-                 2.5 * fl_f / res[False] / 1e6))
+    print(line.rstrip())
