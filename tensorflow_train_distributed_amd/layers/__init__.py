@@ -330,12 +330,20 @@ class MultiHeadAttention(Layer):
     num_kv_heads (None: num_heads) is grouped-query attention, 1 multi-query attention: num_heads
     query heads share num_kv_heads key/value heads (query head h uses h // (num_heads //
     num_kv_heads)), and qkv/kernel shrinks to (D, inner + 2*inner_kv) columns — queries, then keys,
-    then values — with inner_kv = num_kv_heads*key_dim; the same four variables."""
+    then values — with inner_kv = num_kv_heads*key_dim; the same four variables.
+    rotary=True applies rotary position embeddings (ttd.nn.rotary_embedding, base rotary_base) to
+    the projected queries and keys before the attention: in self-attention one call on the
+    [q | k] column slice of the fused projection (num_heads + num_kv_heads heads, one kernel
+    launch on the GPU); in cross-attention the queries at positions 0..S-1 and the keys at
+    0..Sk-1. It adds no variable and composes with use_causal_mask, seqlen, num_kv_heads and
+    dropout."""
     _default_name = "multi_head_attention"
 
-    def __init__(self, num_heads, key_dim=64, dropout=0.0, num_kv_heads=None, name=None):
+    def __init__(self, num_heads, key_dim=64, dropout=0.0, num_kv_heads=None, rotary=False, rotary_base=10000.0,
+                 name=None):
         super().__init__(name)
         self.num_heads, self.key_dim, self.dropout = int(num_heads), int(key_dim), float(dropout)
+        self.rotary, self.rotary_base = bool(rotary), float(rotary_base)
         self.num_kv_heads = self.num_heads if num_kv_heads is None else int(num_kv_heads)
         if self.num_kv_heads <= 0 or self.num_heads % self.num_kv_heads:
             raise InvalidArgumentError(
@@ -358,7 +366,11 @@ class MultiHeadAttention(Layer):
         inner_kv = self.num_kv_heads * self.key_dim
         if value is None:
             qkv = N.dense(x, self.qkv_kernel, self.qkv_bias)
-            q, k, v = qkv[..., :inner], qkv[..., inner:inner + inner_kv], qkv[..., inner + inner_kv:]
+            v = qkv[..., inner + inner_kv:]
+            if self.rotary:  # q and k are adjacent: one rotation over num_heads + num_kv_heads heads
+                qkv = N.rotary_embedding(qkv[..., :inner + inner_kv], self.num_heads + self.num_kv_heads,
+                                         self.rotary_base)
+            q, k = qkv[..., :inner], qkv[..., inner:inner + inner_kv]
         else:
             if value.dim() != x.dim() or value.shape[-1] != x.shape[-1] or value.shape[0] != x.shape[0]:
                 raise InvalidArgumentError(
@@ -368,7 +380,10 @@ class MultiHeadAttention(Layer):
             q = N.dense(x, self.qkv_kernel[:, :inner].contiguous(), self.qkv_bias[:inner].contiguous())
             kv = N.dense(value, self.qkv_kernel[:, inner:].contiguous(), self.qkv_bias[inner:].contiguous())
             k, v = kv[..., :inner_kv], kv[..., inner_kv:]
-        a = N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
+            if self.rotary:  # each side by its own positions: 0..S-1 and 0..Sk-1
+                q = N.rotary_embedding(q, self.num_heads, self.rotary_base)
+                k = N.rotary_embedding(k, self.num_kv_heads, self.rotary_base)
+        a =N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
                         self.dropout if training else 0.0, seqlen=seqlen, causal=use_causal_mask,
                         num_kv_heads=self.num_kv_heads)
         return N.dense(a, self.out_kernel, self.out_bias)

@@ -54,6 +54,12 @@ class BertConfig:
     # causal self-attention (position s attends positions <= s): with labels on next-token
     # positions the MLM head then trains a left-to-right language model
     causal: bool = False
+    # rotary position embeddings (half-split convention, ops.transformer.rope) on q and k of every
+    # layer, before attention. The parameter set does NOT change with the flag: the learned
+    # position table stays and is still added to the embeddings, so checkpoints and the flat
+    # parameter store are the same either way.
+    rotary: bool = False
+    rotary_base: float = 10000.0
 
     @property
     def vocab_padded(self) -> int:
@@ -188,6 +194,11 @@ class BertPretraining:
         if self.device.type == "cuda":
             from ..ops.transformer import RngState
             self.rng = RngState(seed * 7919 + 17, self.device)
+        # cos / sin of every position, built here so that no copy happens inside a captured step
+        self.rope_table = None
+        if cfg.rotary:
+            from ..ops.transformer import rope_table
+            self.rope_table = rope_table(cfg.max_position_embeddings, cfg.rotary_base, self.device)
 
     def _plain(self, x, w, b, b16):
         """y = x w^T + b (w [out][in] bf16; b fp32, b16 its bf16 compute copy) for the forward's
@@ -451,6 +462,8 @@ class BertPretraining:
             qkv = self._plain(x, self._fused(l, "w"), self._fused(l, "b"), self._fused(l, "cb"))
             ao = torch.empty((Tk, H), dtype=bf, device=dev)
             lse = torch.empty((B * NH, S), dtype=torch.float32, device=dev)
+            if c.rotary:  # q and k in place; the rotated qkv is what the attention backward reads too
+                T.rope(qkv, qkv, self.rope_table, S, 2 * NH)
             T.attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, lse, B, NH, S, seqlen=seqlen,
                             p_drop=ad, rng=rng, site=site(l, 0), causal=c.causal)
             nb = self._ln(l, "attention/output/dense/bias")
@@ -574,6 +587,8 @@ class BertPretraining:
             T.attention_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, dao, lse, dqkv[:, :H],
                             dqkv[:, H:2 * H], dqkv[:, 2 * H:], B, NH, S, delta=delta, seqlen=seqlen, p_drop=ad,
                             rng=rng, site=site(l, 0), causal=c.causal)
+            if c.rotary:  # gradients of the rotated q, k -> of the projection's output
+                T.rope(dqkv, dqkv, self.rope_table, S, 2 * NH, inverse=True)
             if self.ln_yield == 2:
                 flush_wgrads()  # (mode 2: the attention backward runs without side-stream GEMMs too)
             del dao, ao, qkv
@@ -602,7 +617,8 @@ class BertPretraining:
     # ------------------------------------------------------------------ fp32 reference (tests)
     def reference_loss(self, batch: BertBatch, leaves: dict):
         """Plain-PyTorch fp32 forward (dropout off) on `leaves` (name -> fp32 tensor with
-        requires_grad as wanted). Returns (mlm mean loss, nsp mean loss)."""
+        requires_grad as wanted). Returns (mlm mean loss, nsp mean loss). With cfg.rotary, q and k
+        are rotated in fp32 torch ops by the engine's own cos / sin table."""
         import torch.nn.functional as F
         c = self.cfg
         H, NH, L, V = c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.vocab_size
@@ -627,11 +643,22 @@ class BertPretraining:
             ar = torch.arange(S, device=x.device)
             keymask = ar[None, :] < batch.seqlen[:, None].long()
         tri = torch.ones((S, S), dtype=torch.bool, device=x.device).tril() if c.causal else None
+        if c.rotary:
+            from ..ops.transformer import rope_table
+            tab = rope_table(c.max_position_embeddings, c.rotary_base, x.device)[:S]
+            cos, sin = tab[:, 0], tab[:, 1]  # [S, 32] against [B, NH, S, 32]
+
+        def rot(t):
+            if not c.rotary:
+                return t
+            lo, hi = t[..., :32], t[..., 32:]
+            return torch.cat([lo * cos - hi * sin, hi * cos + lo * sin], dim=-1)
         for l in range(L):
             p = lambda s, l=l: self._ln(l, s)  # noqa: E731
             q = lin(x, p("attention/self/query")).view(B, S, NH, 64).transpose(1, 2)
             k = lin(x, p("attention/self/key")).view(B, S, NH, 64).transpose(1, 2)
             v = lin(x, p("attention/self/value")).view(B, S, NH, 64).transpose(1, 2)
+            q, k = rot(q), rot(k)
             sc = q @ k.transpose(-1, -2) / 8.0
             if keymask is not None:
                 sc = sc.masked_fill(~keymask[:, None, None, :], float("-inf"))

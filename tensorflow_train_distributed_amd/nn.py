@@ -20,6 +20,7 @@ accumulation) for either input dtype.
     ttd.nn.conv2d(x, kernel, strides, padding)            # NHWC, kernel [R, S, C, K]
     ttd.nn.attention(q, k, v, num_heads, dropout_rate)    # [B, S, H*64] token-major
     ttd.nn.attention(q, k, v, 16, num_kv_heads=4)         # grouped-query: k, v [B, Sk, 4*64]
+    ttd.nn.rotary_embedding(q, 16, offset=0)              # RoPE on q / k before attention
 """
 from __future__ import annotations
 
@@ -776,6 +777,88 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
     if dropout_rate > 0:
         p = F.dropout(p, dropout_rate, training=True)
     return (p @ vh).transpose(1, 2).reshape(B, S, D)
+
+
+# ------------------------------------------------------------------ rotary position embeddings
+def _token_rows(t, B, S, D):
+    """[B*S, D] view of t [B, S, D] that the rope kernel can take as it is (unit column stride,
+    uniformly strided 16-byte aligned rows: a column slice of a fused projection is one), else of a
+    contiguous copy."""
+    es = t.element_size()
+    ok = (t.stride(2) == 1 and t.stride(1) >= D and (B == 1 or t.stride(0) == S * t.stride(1))
+          and (t.stride(1) * es) % 16 == 0 and t.data_ptr() % 16 == 0)
+    if not ok:
+        t = t.contiguous()
+    return t.as_strided((B * S, D), (t.stride(1), 1))
+
+
+class _Rotary(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, num_heads, table, offset):
+        from .ops import transformer as T
+        B, S, D = x.shape
+        y = torch.empty((B * S, D), dtype=x.dtype, device=x.device)
+        T.rope(_token_rows(x, B, S, D), y, table, S, num_heads, pos0=offset)
+        ctx.cfg = (num_heads, table, offset)
+        return y.view(B, S, D)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import transformer as T
+        num_heads, table, offset = ctx.cfg
+        B, S, D = dy.shape
+        dx = torch.empty((B * S, D), dtype=dy.dtype, device=dy.device)
+        T.rope(_token_rows(dy, B, S, D), dx, table, S, num_heads, pos0=offset, inverse=True)
+        return dx.view(B, S, D), None, None, None
+
+
+def rotary_embedding(x, num_heads: int, base: float = 10000.0, offset: int = 0):
+    """Rotary position embedding (RoPE) of x [B, S, num_heads*head_dim], half-split convention
+    ("rotate_half", LLaMA / GPT-NeoX): in every head, with half = head_dim // 2, i in [0, half),
+    theta_i = base**(-i/half) and p = offset + s the position of token s,
+        y[i]        = x[i] * cos(p theta_i) - x[i + half] * sin(p theta_i)
+        y[i + half] = x[i + half] * cos(p theta_i) + x[i] * sin(p theta_i).
+    Apply it to q and k before attention (`offset`: the position of the first token, e.g. the
+    length of a cached prefix). The result has x's shape and dtype; the backward is the inverse
+    rotation of the incoming gradient (the rotation is orthogonal), the same kernel with -sin.
+    GPU: head_dim 64 only, any S; bf16 stays bf16 and fp32 stays fp32 (rope.hip, cos / sin from a
+    host-built table: ops.transformer.rope_table, offset + S rows rounded up to a power of two, at
+    least 512). A view with unit column stride and uniformly strided rows — a column slice of a
+    fused projection — is read through its row stride without a copy. CPU: the same convention in
+    fp32 torch ops for any even head_dim."""
+    if x.dim() != 3:
+        raise InvalidArgumentError("ttd.nn.rotary_embedding: x must be [batch, seq_len, num_heads * head_dim] "
+                                   "(got shape %s)" % (tuple(x.shape),))
+    B, S, D = x.shape
+    num_heads, offset = int(num_heads), int(offset)
+    if num_heads <= 0 or D % num_heads:
+        raise InvalidArgumentError(
+            "ttd.nn.rotary_embedding: num_heads must divide the width (got width %d, num_heads %d)" % (D, num_heads))
+    hd = D // num_heads
+    if hd % 2:
+        raise InvalidArgumentError(
+            "ttd.nn.rotary_embedding: head_dim must be even, the rotation pairs column i with i + head_dim/2 "
+            "(got head_dim %d)" % hd)
+    if offset < 0:
+        raise InvalidArgumentError("ttd.nn.rotary_embedding: offset must be >= 0 (got %d)" % offset)
+    if _on_gpu(x):
+        if hd != 64:
+            raise InvalidArgumentError(
+                "ttd.nn.rotary_embedding on GPU runs the rotary kernel for head_dim 64 (got head_dim %d); "
+                "use 64-wide heads" % hd)
+        from .ops import transformer as T
+        rows = max(512, 1 << (offset + S - 1).bit_length())
+        if B * S == 0:
+            return x.clone()
+        return _Rotary.apply(x, num_heads, T.rope_table(rows, base, x.device), offset)
+    half = hd // 2
+    pos = torch.arange(offset, offset + S, dtype=torch.float64)
+    ang = pos[:, None] * float(base) ** (-torch.arange(half, dtype=torch.float64) / half)
+    cos, sin = ang.cos().float()[None, :, None, :], ang.sin().float()[None, :, None, :]
+    xh = x.float().reshape(B, S, num_heads, hd)
+    lo, hi = xh[..., :half], xh[..., half:]
+    y = torch.cat([lo * cos - hi * sin, hi * cos + lo * sin], dim=-1)
+    return y.reshape(B, S, D).to(x.dtype)
 
 
 class _Embedding(torch.autograd.Function):

@@ -1,4 +1,4 @@
-"""Launch wrappers for the transformer kernels (attention.hip, transformer.hip) plus exact
+"""Launch wrappers for the transformer kernels (attention.hip, transformer.hip, rope.hip) plus exact
 CPU re-implementations of their dropout hash (used by the numerics tests as oracles).
 
 All device tensors are bf16 token-major [tokens, features] unless noted; statistics fp32.
@@ -29,6 +29,8 @@ _lib.register({
     "ttdk_xent_vocab": [P, L, I, P, I, P, P, P, P, P],
     "ttdk_tanh_bf16": [P, L, P],
     "ttdk_dact_bf16": [P, P, P, L, I, P],
+    "ttdk_rope": [P, L, P, L, I, P, I, L, I, I, I, I, P],
+    "ttdk_rope_max_threads": [],
 })
 
 
@@ -100,6 +102,56 @@ def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=Non
               B, H, int(H if Hk is None else Hk), S, int(S if Sk is None else Sk), float(p_drop),
               _p(rng.t if rng is not None else None), int(site), int(bool(causal)), _s())
     return dq, dk, dv
+
+
+# ------------------------------------------------------------------ rotary position embeddings
+_ROPE_DT = {torch.float32: 0, torch.bfloat16: 1}
+_rope_tables = {}  # (device, base, rows) -> table; never evicted (a captured hipGraph may hold the pointer)
+
+
+def rope_table(rows, base=10000.0, device="cuda"):
+    """fp32 [rows, 2, 32] table of the rotary embedding (rope.hip): [p, 0, i] = cos(p * base**(-i/32)),
+    [p, 1, i] the sine, computed on the host in float64 and rounded once to fp32. Cached per
+    (device, base, rows) and never evicted, because a captured hipGraph may hold the pointer; a
+    cache miss while the current stream is capturing raises instead of copying inside the capture
+    (build the table before the capture). A CPU device gives the same table."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (str(dev), float(base), int(rows))
+    t = _rope_tables.get(key)
+    if t is None:
+        if rows <= 0 or not base > 0:
+            raise ValueError("rope_table needs rows > 0 and base > 0 (got rows %r, base %r)" % (rows, base))
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(
+                "rope_table(%d, base=%r) is not cached and the current stream is capturing a graph: the table's "
+                "host-to-device copy cannot run inside a capture; build the table before the capture" % (rows, base))
+        ang = np.arange(int(rows), dtype=np.float64)[:, None] * float(base) ** (-np.arange(32, dtype=np.float64) / 32.0)
+        t = torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)).to(dev)
+        _rope_tables[key] = t
+    return t
+
+
+def rope(x, y, table, S, heads, *, pos0=0, inverse=False):
+    """y[r, :heads*64] = the half-split rotation of x[r, :heads*64] at position pos0 + r % S
+    (inverse=True: the inverse rotation, which is also the backward). x, y: 2-D views [tokens,
+    >= heads*64] of one dtype (bf16 or fp32) with unit column stride, each with its own row stride;
+    columns from heads*64 on are not touched. y may be x (in place, e.g. x = qkv with heads =
+    H + Hk rotates q and k of the fused projection in one launch); any other overlap of x and y is
+    the caller's error. table: rope_table(rows >= pos0 + S) on x's device."""
+    if x.dtype != y.dtype or x.dtype not in _ROPE_DT or x.dim() != 2 or y.shape[0] != x.shape[0] \
+            or x.stride(1) != 1 or y.stride(1) != 1 or table.dtype != torch.float32 or not table.is_contiguous():
+        raise _lib.HipKernelError("rope: x and y must be 2-D bf16 or fp32 views of one dtype and row count with unit "
+                                  "column stride, table contiguous fp32")
+    _lib.call("ttdk_rope", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _ROPE_DT[x.dtype],
+              table.data_ptr(), table.shape[0], x.shape[0], int(S), int(heads), int(pos0), int(bool(inverse)), _s())
+    return y
+
+
+def rope_max_threads():
+    """Threads the capped rope grid launches; more work items than this are grid-strided."""
+    return _lib.query("ttdk_rope_max_threads")
 
 
 # ------------------------------------------------------------------ LayerNorm
