@@ -300,6 +300,47 @@ class LayerNormalization(Layer):
         return N.layer_norm(x, self.gamma, self.beta, self.epsilon)
 
 
+class RMSNormalization(Layer):
+    """RMSNorm over the last axis: x * rsqrt(mean(x^2) + epsilon) * gamma (no centring, no beta)."""
+    _default_name = "rms_normalization"
+
+    def __init__(self, epsilon=1e-6, name=None):
+        super().__init__(name)
+        self.epsilon = float(epsilon)
+
+    def build(self, input_shape):
+        self.add_weight("gamma", (input_shape[-1],), "ones")
+        super().build(input_shape)
+
+    def call(self, x, **kw):
+        return N.rms_norm(x, self.gamma, self.epsilon)
+
+
+class SwiGLU(Layer):
+    """Gated SiLU unit: silu(x Wg + bg) * (x Wv + bv) as ONE fused projection, like `qkv/kernel`:
+    kernel [in, 2*units] and bias [2*units] hold the gate columns first, then the value columns."""
+    _default_name = "swiglu"
+
+    def __init__(self, units, use_bias=True, kernel_initializer="glorot_uniform", bias_initializer="zeros",
+                 kernel_regularizer=None, bias_regularizer=None, name=None, trainable=True):
+        super().__init__(name, trainable)
+        self.units = int(units)
+        self.use_bias = use_bias
+        self.kernel_initializer, self.bias_initializer = kernel_initializer, bias_initializer
+        self.kernel_regularizer, self.bias_regularizer = kernel_regularizer, bias_regularizer
+
+    def build(self, input_shape):
+        self.add_weight("kernel", (input_shape[-1], 2 * self.units), self.kernel_initializer, self.kernel_regularizer)
+        if self.use_bias:
+            self.add_weight("bias", (2 * self.units,), self.bias_initializer, self.bias_regularizer)
+        else:
+            self.bias = None
+        super().build(input_shape)
+
+    def call(self, x, **kw):
+        return N.swiglu(N.dense(x, self.kernel, self.bias))
+
+
 class Embedding(Layer):
     _default_name = "embedding"
 

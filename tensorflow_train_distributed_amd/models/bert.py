@@ -60,6 +60,17 @@ class BertConfig:
     # parameter store are the same either way.
     rotary: bool = False
     rotary_base: float = 10000.0
+    # RMSNorm (ops.transformer.rmsnorm_fwd / rmsnorm_bwd, with layer_norm_eps) at every LayerNorm
+    # site: the embeddings, two per layer and the MLM transform. The parameter set does NOT change
+    # with the flag: every .../LayerNorm/beta stays, is not read, and its gradient is written as
+    # exact zeros every step.
+    rms_norm: bool = False
+    # gated feed-forward (SwiGLU): intermediate/dense becomes one fused [2I, H] projection, gate
+    # rows first (TF shape [H, 2I]; bias [2I]), and the unit is silu(gate) * value in place of
+    # bias + GELU; output/dense is unchanged. The MLM transform keeps GELU. Saves the [tokens, 2I]
+    # projection and the [tokens, I] unit for the backward: 3 * tokens * I elements per layer
+    # against 2 * tokens * I without the flag.
+    gated_ffn: bool = False
 
     @property
     def vocab_padded(self) -> int:
@@ -247,8 +258,8 @@ class BertPretraining:
             ln(p("output/LayerNorm"))
             dense(p("output/dense"), H, I)
             bias(p("output/dense/bias"), H)
-            dense(p("intermediate/dense"), I, H)
-            bias(p("intermediate/dense/bias"), I)
+            dense(p("intermediate/dense"), 2 * I if c.gated_ffn else I, H)
+            bias(p("intermediate/dense/bias"), 2 * I if c.gated_ffn else I)
             ln(p("attention/output/LayerNorm"))
             dense(p("attention/output/dense"), H, H)
             bias(p("attention/output/dense/bias"), H)
@@ -300,10 +311,11 @@ class BertPretraining:
         for w, t in rest:
             K.krsc_to_crsk(w.view(w.shape[0], 1, 1, w.shape[1]), out=t.view(t.shape[0], 1, 1, t.shape[1]))
 
-    def _inter_buf(self, rows):
-        """[rows, intermediate] bf16 activation whose row stride is padded by inter_pad elements
-        (a column view of a wider buffer; every GEMM here takes row-strided operands)."""
-        I = self.cfg.intermediate_size
+    def _inter_buf(self, rows, width=None):
+        """[rows, width] (default: intermediate) bf16 activation whose row stride is padded by
+        inter_pad elements (a column view of a wider buffer; every GEMM here takes row-strided
+        operands)."""
+        I = self.cfg.intermediate_size if width is None else width
         pad = self.inter_pad if self.device.type == "cuda" else 0
         buf = torch.empty((rows, I + pad), dtype=torch.bfloat16, device=self.device)
         return buf[:, :I] if pad else buf
@@ -450,12 +462,26 @@ class BertPretraining:
         pos_grp = (batch.masked_lm_positions.shape[1], S)
         labels = batch.masked_lm_ids.reshape(-1).contiguous()
 
+        def norm_fwd(x, name, **kw):
+            """(y, s, mean, rstd) of the normalisation site `name`; mean is None under cfg.rms_norm."""
+            if c.rms_norm:
+                y_, s_, r_ = T.rmsnorm_fwd(x, P.var[name + "/gamma"], eps=eps, **kw)
+                return y_, s_, None, r_
+            return T.layernorm_fwd(x, P.var[name + "/gamma"], P.var[name + "/beta"], eps=eps, **kw)
+
+        def norm_bwd(dy, s, mean, rstd, name, **kw):
+            """(ds, dx) of the site; writes its gamma / beta gradients. Under cfg.rms_norm beta is not
+            part of the function: its gradient slot is zeroed (stale values would reach the optimizer)."""
+            if c.rms_norm:
+                K.zero_(P.g[name + "/beta"])
+                return T.rmsnorm_bwd(dy, s, rstd, P.var[name + "/gamma"], P.g[name + "/gamma"], **kw)
+            return T.layernorm_bwd(dy, s, mean, rstd, P.var[name + "/gamma"], P.g[name + "/gamma"],
+                                   P.g[name + "/beta"], **kw)
+
         # ---------------------------------------------------------------- forward
         s0 = T.embed_fwd(ids, tt, P.c["bert/embeddings/word_embeddings"], P.c["bert/embeddings/position_embeddings"],
                          P.c["bert/embeddings/token_type_embeddings"], S)
-        y, _, mean0, rstd0 = T.layernorm_fwd(s0, P.var["bert/embeddings/LayerNorm/gamma"],
-                                             P.var["bert/embeddings/LayerNorm/beta"], eps=eps, p_out=hd,
-                                             site_out=1, rng=rng)
+        y, _, mean0, rstd0 = norm_fwd(s0, "bert/embeddings/LayerNorm", p_out=hd, site_out=1, rng=rng)
         ctx = []
         for l in range(L):
             x = y
@@ -468,18 +494,27 @@ class BertPretraining:
                             p_drop=ad, rng=rng, site=site(l, 0), causal=c.causal)
             nb = self._ln(l, "attention/output/dense/bias")
             proj = self._plain(ao, P.c[self._ln(l, "attention/output/dense/kernel")], P.var[nb], P.c[nb])
-            y1, s1, m1, r1 = T.layernorm_fwd(proj, P.var[self._ln(l, "attention/output/LayerNorm/gamma")],
-                                             P.var[self._ln(l, "attention/output/LayerNorm/beta")], res=x, eps=eps,
-                                             p_in=hd, site_in=site(l, 1), rng=rng)
+            y1, s1, m1, r1 = norm_fwd(proj, self._ln(l, "attention/output/LayerNorm"), res=x, p_in=hd,
+                                      site_in=site(l, 1), rng=rng)
             del proj
-            pre = self._inter_buf(Tk)
-            inter = G.gemm(y1, P.c[self._ln(l, "intermediate/dense/kernel")], trans_b=True, out=self._inter_buf(Tk),
-                           bias=P.var[self._ln(l, "intermediate/dense/bias")], act=G.ACT_GELU, aux=pre)
+            if c.gated_ffn:
+                # one plain bias GEMM for [gate | value], then the gated unit; both are kept for backward
+                pre = self._inter_buf(Tk, 2 * c.intermediate_size)
+                nb = self._ln(l, "intermediate/dense/bias")
+                if self.blaslt:
+                    torch.addmm(P.c[nb], y1, P.c[self._ln(l, "intermediate/dense/kernel")].t(), out=pre)
+                else:
+                    G.gemm(y1, P.c[self._ln(l, "intermediate/dense/kernel")], trans_b=True, out=pre, bias=P.var[nb])
+                inter = T.swiglu_fwd(pre, out=self._inter_buf(Tk))
+            else:
+                pre = self._inter_buf(Tk)
+                inter = G.gemm(y1, P.c[self._ln(l, "intermediate/dense/kernel")], trans_b=True,
+                               out=self._inter_buf(Tk), bias=P.var[self._ln(l, "intermediate/dense/bias")],
+                               act=G.ACT_GELU, aux=pre)
             nb = self._ln(l, "output/dense/bias")
             o2 = self._plain(inter, P.c[self._ln(l, "output/dense/kernel")], P.var[nb], P.c[nb])
-            y, s2, m2, r2 = T.layernorm_fwd(o2, P.var[self._ln(l, "output/LayerNorm/gamma")],
-                                            P.var[self._ln(l, "output/LayerNorm/beta")], res=y1, eps=eps, p_in=hd,
-                                            site_in=site(l, 2), rng=rng)
+            y, s2, m2, r2 = norm_fwd(o2, self._ln(l, "output/LayerNorm"), res=y1, p_in=hd, site_in=site(l, 2),
+                                     rng=rng)
             del o2
             ctx.append((x, qkv, ao, lse, s1, m1, r1, y1, pre, inter, s2, m2, r2))
 
@@ -488,8 +523,7 @@ class BertPretraining:
         tpre = torch.empty_like(hm)
         t = G.gemm(hm, P.c["cls/predictions/transform/dense/kernel"], trans_b=True,
                    bias=P.var["cls/predictions/transform/dense/bias"], act=G.ACT_GELU, aux=tpre)
-        t2, _, mt, rt = T.layernorm_fwd(t, P.var["cls/predictions/transform/LayerNorm/gamma"],
-                                        P.var["cls/predictions/transform/LayerNorm/beta"], eps=eps)
+        t2, _, mt, rt = norm_fwd(t, "cls/predictions/transform/LayerNorm")
         logits = self._plain(t2, P.c["bert/embeddings/word_embeddings"], P.var["cls/predictions/output_bias"],
                              P.c["cls/predictions/output_bias"])
         sums = K.zeros(4, dtype=torch.float32, device=dev)  # own memset: no torch fill kernel in the step
@@ -514,9 +548,7 @@ class BertPretraining:
         dt2 = (torch.mm(dlog, P.c["bert/embeddings/word_embeddings"]) if self.blaslt >= 2
                else G.gemm(dlog, P.c["bert/embeddings/word_embeddings"]))
         del dlog, logits
-        dt, _ = T.layernorm_bwd(dt2, t, mt, rt, P.var["cls/predictions/transform/LayerNorm/gamma"],
-                                g["cls/predictions/transform/LayerNorm/gamma"],
-                                g["cls/predictions/transform/LayerNorm/beta"])
+        dt, _ = norm_bwd(dt2, t, mt, rt, "cls/predictions/transform/LayerNorm")
         hook("cls/predictions/transform/LayerNorm/beta")
         dtp = T.dact(dt, tpre, 0)
         wgrad(dtp, hm, g["cls/predictions/transform/dense/kernel"])
@@ -537,9 +569,10 @@ class BertPretraining:
         T.scatter_rows(dcls, None, dy, accumulate=True, group=(1, S))
 
         # ---------------------------------------------------------------- backward: encoder
-        ln_work = T.ln_bwd_workspace(Tk, H, dev)
-        # FFN1 bias gradient from the FFN2-dgrad epilogue statistics (256-row GEMM tiles)
-        fuse_bias = self.fuse_bias_grad and G.big_fits(Tk, c.intermediate_size, H)
+        ln_work = T.rmsnorm_bwd_workspace(Tk, H, dev) if c.rms_norm else T.ln_bwd_workspace(Tk, H, dev)
+        # FFN1 bias gradient from the FFN2-dgrad epilogue statistics (256-row GEMM tiles); the gated
+        # feed-forward has no activation epilogue on that data gradient, so the switch is ignored there
+        fuse_bias = self.fuse_bias_grad and not c.gated_ffn and G.big_fits(Tk, c.intermediate_size, H)
         bias_part = (torch.empty((-(-Tk // 256), 2, c.intermediate_size), dtype=torch.float32, device=dev)
                      if fuse_bias else None)
         delta = torch.empty((B * NH, S), dtype=torch.float32, device=dev)
@@ -548,15 +581,19 @@ class BertPretraining:
         for l in reversed(range(L)):
             x, qkv, ao, lse, s1, m1, r1, y1, pre, inter, s2, m2, r2 = ctx.pop()
             G1 = torch.empty((Tk, H), dtype=bf, device=dev)
-            _, dout2 = T.layernorm_bwd(dy, s2, m2, r2, P.var[self._ln(l, "output/LayerNorm/gamma")],
-                                       g[self._ln(l, "output/LayerNorm/gamma")],
-                                       g[self._ln(l, "output/LayerNorm/beta")], ds_out=G1, want_dx=True, p_in=hd,
-                                       site_in=site(l, 2), rng=rng, work=ln_work)
+            _, dout2 = norm_bwd(dy, s2, m2, r2, self._ln(l, "output/LayerNorm"), ds_out=G1, want_dx=True, p_in=hd,
+                                site_in=site(l, 2), rng=rng, work=ln_work)
             flush_wgrads()
             del dy
             wgrad_bias(dout2, inter, g[self._ln(l, "output/dense/kernel")], g[self._ln(l, "output/dense/bias")])
             b_inter = g[self._ln(l, "intermediate/dense/bias")]
-            if fuse_bias:
+            if c.gated_ffn:
+                # d(unit) from FFN2's data gradient with no activation epilogue, then [dgate | dvalue]
+                # written over the saved [gate | value] projection
+                dinter = self._dgrad(dout2, l, 3, out=self._inter_buf(Tk))
+                dpre = T.swiglu_bwd(dinter, pre, out=pre)
+                del dinter
+            elif fuse_bias:
                 # the intermediate bias gradient = column sums of dpre, taken from the per-tile
                 # statistics of the dGELU dgrad epilogue that produces dpre (no separate column-sum
                 # pass over the [tokens, 4096] gradient)
@@ -572,10 +609,8 @@ class BertPretraining:
             del dpre
             layer_hook(self._ln(l, "intermediate/dense/bias"))
             G0 = torch.empty((Tk, H), dtype=bf, device=dev)
-            _, dproj = T.layernorm_bwd(G1, s1, m1, r1, P.var[self._ln(l, "attention/output/LayerNorm/gamma")],
-                                       g[self._ln(l, "attention/output/LayerNorm/gamma")],
-                                       g[self._ln(l, "attention/output/LayerNorm/beta")], ds_out=G0, want_dx=True,
-                                       p_in=hd, site_in=site(l, 1), rng=rng, work=ln_work)
+            _, dproj = norm_bwd(G1, s1, m1, r1, self._ln(l, "attention/output/LayerNorm"), ds_out=G0, want_dx=True,
+                                p_in=hd, site_in=site(l, 1), rng=rng, work=ln_work)
             if self.ln_yield != 2:
                 flush_wgrads()
             del G1
@@ -603,9 +638,8 @@ class BertPretraining:
         keep.clear()
 
         # ---------------------------------------------------------------- backward: embeddings
-        ds0, _ = T.layernorm_bwd(dy, s0, mean0, rstd0, P.var["bert/embeddings/LayerNorm/gamma"],
-                                 g["bert/embeddings/LayerNorm/gamma"], g["bert/embeddings/LayerNorm/beta"], p_out=hd,
-                                 site_out=1, rng=rng, work=ln_work)
+        ds0, _ = norm_bwd(dy, s0, mean0, rstd0, "bert/embeddings/LayerNorm", p_out=hd, site_out=1, rng=rng,
+                          work=ln_work)
         dpos = g["bert/embeddings/position_embeddings"]
         if S < dpos.shape[0]:
             K.zero_(dpos[S:])
@@ -618,7 +652,8 @@ class BertPretraining:
     def reference_loss(self, batch: BertBatch, leaves: dict):
         """Plain-PyTorch fp32 forward (dropout off) on `leaves` (name -> fp32 tensor with
         requires_grad as wanted). Returns (mlm mean loss, nsp mean loss). With cfg.rotary, q and k
-        are rotated in fp32 torch ops by the engine's own cos / sin table."""
+        are rotated in fp32 torch ops by the engine's own cos / sin table; cfg.rms_norm and
+        cfg.gated_ffn take the matching fp32 branches (RMSNorm without beta, silu(gate) * value)."""
         import torch.nn.functional as F
         c = self.cfg
         H, NH, L, V = c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.vocab_size
@@ -629,6 +664,8 @@ class BertPretraining:
             return x @ W[name + "/kernel"].t() + W[name + "/bias"]
 
         def ln(x, name):
+            if c.rms_norm:  # beta is not read
+                return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + c.layer_norm_eps) * W[name + "/gamma"]
             return F.layer_norm(x, (H,), W[name + "/gamma"], W[name + "/beta"], c.layer_norm_eps)
 
         def gelu(x):
@@ -666,7 +703,11 @@ class BertPretraining:
                 sc = sc.masked_fill(~tri, float("-inf"))
             a = (sc.softmax(-1) @ v).transpose(1, 2).reshape(B, S, H)
             x = ln(x + lin(a, p("attention/output/dense")), p("attention/output/LayerNorm"))
-            h = gelu(lin(x, p("intermediate/dense")))
+            h = lin(x, p("intermediate/dense"))
+            if c.gated_ffn:  # [gate | value] columns of the fused projection
+                h = F.silu(h[..., :c.intermediate_size]) * h[..., c.intermediate_size:]
+            else:
+                h = gelu(h)
             x = ln(x + lin(h, p("output/dense")), p("output/LayerNorm"))
         flat = x.reshape(B * S, H)
         offs = torch.arange(B, device=x.device) * S

@@ -21,6 +21,7 @@ accumulation) for either input dtype.
     ttd.nn.attention(q, k, v, num_heads, dropout_rate)    # [B, S, H*64] token-major
     ttd.nn.attention(q, k, v, 16, num_kv_heads=4)         # grouped-query: k, v [B, Sk, 4*64]
     ttd.nn.rotary_embedding(q, 16, offset=0)              # RoPE on q / k before attention
+    ttd.nn.rms_norm(x, gamma); ttd.nn.swiglu(x)           # RMSNorm; silu(x[..., :I]) * x[..., I:]
 """
 from __future__ import annotations
 
@@ -450,6 +451,110 @@ def layer_norm(x, gamma, beta, eps: float = 1e-12):
             return _LayerNorm.apply(x, gamma, beta, float(eps))   # vectorised BERT kernel
         return _LayerNormGeneric.apply(x, gamma, beta, float(eps))
     return F.layer_norm(x, (x.shape[-1],), gamma, beta, eps)
+
+
+class _RMSNorm(torch.autograd.Function):
+    """bf16 at a fast width (rmsnorm_glu.hip): wave per row, the row in registers."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, eps):
+        from .ops import transformer as T
+        shp = x.shape
+        xb = x.reshape(-1, shp[-1]).contiguous()
+        g = _f32(gamma)
+        y, s, rstd = T.rmsnorm_fwd(xb, g, eps=eps)
+        ctx.save_for_backward(s, rstd, g)
+        ctx.cfg = (shp, gamma.dtype)
+        return y.reshape(shp)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import transformer as T
+        s, rstd, g = ctx.saved_tensors
+        shp, gdt = ctx.cfg
+        H = shp[-1]
+        dg = torch.empty(H, dtype=torch.float32, device=dy.device)
+        ds, _ = T.rmsnorm_bwd(dy.reshape(-1, H).to(torch.bfloat16).contiguous(), s, rstd, g, dg)
+        return ds.reshape(shp), dg.to(gdt), None
+
+
+class _RMSNormGeneric(torch.autograd.Function):
+    """Any width, fp32 or bf16 (rmsnorm_glu.hip): wave-per-row statistic, deterministic
+    column-partial dgamma."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, eps):
+        from .ops import kernels as K
+        shp = x.shape
+        x2 = x.reshape(-1, shp[-1]).contiguous()
+        g = _f32(gamma)
+        y, rstd = K.rms_generic_fwd(x2, g, eps)
+        ctx.save_for_backward(x2, g, rstd)
+        ctx.cfg = (shp, gamma.dtype)
+        return y.reshape(shp)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import kernels as K
+        x2, g, rstd = ctx.saved_tensors
+        shp, gdt = ctx.cfg
+        H = shp[-1]
+        dg = torch.empty(H, dtype=torch.float32, device=dy.device)
+        d2 = dy.reshape(-1, H).contiguous().to(x2.dtype)
+        dx = K.rms_generic_bwd(d2, x2, g, rstd, dg, want_dx=ctx.needs_input_grad[0])
+        return (dx.reshape(shp) if dx is not None else None), dg.to(gdt), None
+
+
+def rms_norm(x, gamma, eps: float = 1e-6):
+    """y = x * rsqrt(mean(x^2, -1) + eps) * gamma over the last axis (RMSNorm; statistic in fp32).
+    GPU: bf16 at a LayerNorm fast width runs the vectorised kernel, any other width or fp32 the
+    generic one (fp32 stays fp32). CPU: the fp32 formula in torch ops."""
+    if x.dim() < 1 or x.shape[-1] < 1 or gamma.dim() != 1 or gamma.shape[0] != x.shape[-1]:
+        raise InvalidArgumentError("ttd.nn.rms_norm: gamma must be [%s] for x %s, got %s"
+                                   % (x.shape[-1] if x.dim() else "?", tuple(x.shape), tuple(gamma.shape)))
+    if _on_gpu(x):
+        if x.numel() == 0:
+            raise InvalidArgumentError("ttd.nn.rms_norm: empty input %s" % (tuple(x.shape),))
+        if x.dtype == torch.bfloat16 and x.shape[-1] in _LN_FAST_WIDTHS:
+            return _RMSNorm.apply(x, gamma, float(eps))
+        return _RMSNormGeneric.apply(x, gamma, float(eps))
+    xf = x.float()
+    y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gamma.float()
+    return y.to(x.dtype)
+
+
+class _SwiGLU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        from .ops import transformer as T
+        shp = x.shape
+        x2 = x.reshape(-1, shp[-1]).contiguous()
+        h = T.swiglu_fwd(x2)
+        ctx.save_for_backward(x2)
+        ctx.shp = shp
+        return h.reshape(shp[:-1] + (shp[-1] // 2,))
+
+    @staticmethod
+    def backward(ctx, dh):
+        from .ops import transformer as T
+        (x2,) = ctx.saved_tensors
+        shp = ctx.shp
+        d2 = dh.reshape(-1, shp[-1] // 2).contiguous().to(x2.dtype)
+        return T.swiglu_bwd(d2, x2).reshape(shp)
+
+
+def swiglu(x):
+    """silu(a) * b for x = [a | b] split in halves along the last axis (gate first): the gated unit of
+    a LLaMA-style feed-forward. GPU bf16 / fp32 run the SwiGLU kernel; CPU is F.silu(a) * b."""
+    if x.dim() < 1 or x.shape[-1] % 2 or x.shape[-1] == 0:
+        raise InvalidArgumentError("ttd.nn.swiglu: the last dimension must be even and non-zero, got %s"
+                                   % (tuple(x.shape),))
+    if _on_gpu(x):
+        if x.numel() == 0:
+            raise InvalidArgumentError("ttd.nn.swiglu: empty input %s" % (tuple(x.shape),))
+        return _SwiGLU.apply(x)
+    a, b = x.chunk(2, dim=-1)
+    return F.silu(a) * b
 
 
 class _BatchNorm(torch.autograd.Function):

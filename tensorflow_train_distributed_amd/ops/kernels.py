@@ -500,6 +500,10 @@ _lib.register({
     "ttdk_gap_bwd": [_lib.P, _lib.P, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P],
     "ttdk_ln_generic_fwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.F, _lib.P],
     "ttdk_ln_generic_bwd_dx": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.P],
+    "ttdk_rms_generic_fwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.F, _lib.P],
+    "ttdk_rms_generic_parts": [_lib.L, _lib.I],
+    "ttdk_rms_generic_bwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.I, _lib.L, _lib.I,
+                             _lib.P],
     "ttdk_gather_generic": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.I, _lib.L, _lib.I, _lib.L, _lib.P],
     "ttdk_scatter_add_generic": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.I, _lib.L, _lib.I, _lib.L, _lib.P],
     "ttdk_in_top_k": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.I, _lib.L, _lib.I, _lib.I, _lib.P],
@@ -608,6 +612,28 @@ def ln_generic_bwd(dy2d, x2d, gamma, mean, rstd, dgamma, dbeta, want_dx=True):
                   rstd.data_ptr(), dx.data_ptr(), _dt(dy2d, x2d), rows, H, _s())
     part, T = col_stats(dy2d, x2d, mode=2, mu=mean, rs=rstd)
     col_reduce2(part, T, o0=dbeta, o1=dgamma)
+    return dx
+
+
+def rms_generic_fwd(x2d, gamma, eps):
+    """RMSNorm of any width, fp32 or bf16 (rmsnorm_glu.hip): y = x * rsqrt(mean(x^2) + eps) * gamma.
+    Returns (y, rstd)."""
+    rows, H = x2d.shape
+    y = torch.empty_like(x2d)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x2d.device)
+    _lib.call("ttdk_rms_generic_fwd", x2d.data_ptr(), gamma.data_ptr(), y.data_ptr(), rstd.data_ptr(), _dt(x2d),
+              rows, H, float(eps), _s())
+    return y, rstd
+
+
+def rms_generic_bwd(dy2d, x2d, gamma, rstd, dgamma, want_dx=True, accumulate=False):
+    """dx (None unless want_dx) and dgamma (fp32 [H], column partials summed in a fixed order)."""
+    rows, H = x2d.shape
+    dx = torch.empty_like(x2d) if want_dx else None
+    T = _lib.query("ttdk_rms_generic_parts", rows, H)
+    part = torch.empty((T, H), dtype=torch.float32, device=x2d.device)
+    _lib.call("ttdk_rms_generic_bwd", dy2d.data_ptr(), x2d.data_ptr(), gamma.data_ptr(), rstd.data_ptr(), _p(dx),
+              part.data_ptr(), dgamma.data_ptr(), int(accumulate), _dt(dy2d, x2d), rows, H, _s())
     return dx
 
 

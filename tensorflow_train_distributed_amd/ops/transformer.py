@@ -1,4 +1,5 @@
-"""Launch wrappers for the transformer kernels (attention.hip, transformer.hip, rope.hip) plus exact
+"""Launch wrappers for the transformer kernels (attention.hip, transformer.hip, rope.hip,
+rmsnorm_glu.hip) plus exact
 CPU re-implementations of their dropout hash (used by the numerics tests as oracles).
 
 All device tensors are bf16 token-major [tokens, features] unless noted; statistics fp32.
@@ -8,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ..utils.errors import InvalidArgumentError
 from . import _lib
 from ._lib import F, I, L, P
 
@@ -31,6 +33,12 @@ _lib.register({
     "ttdk_dact_bf16": [P, P, P, L, I, P],
     "ttdk_rope": [P, L, P, L, I, P, I, L, I, I, I, I, P],
     "ttdk_rope_max_threads": [],
+    "ttdk_rms_fwd": [P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
+    "ttdk_rms_bwd_num_blocks": [I],
+    "ttdk_rms_bwd": [P, P, P, P, P, P, P, P, I, I, I, F, I, F, I, P, P],
+    "ttdk_swiglu_fwd": [P, L, P, L, I, L, I, P],
+    "ttdk_swiglu_bwd": [P, L, P, L, P, L, I, L, I, P],
+    "ttdk_swiglu_max_threads": [],
 })
 
 
@@ -187,6 +195,150 @@ def layernorm_bwd(dy, s, mean, rstd, gamma, dgamma, dbeta, *, ds_out=None, want_
               dbeta.data_ptr(), int(accumulate), rows, H, float(p_in), int(site_in), float(p_out), int(site_out),
               _p(rng.t if rng is not None else None), _s())
     return ds_out, (dx_out if want_dx else None)
+
+
+# ------------------------------------------------------------------ RMSNorm (rmsnorm_glu.hip, fast widths)
+RMS_FAST_WIDTHS = (512, 1024, 1536, 2048, 4096)
+
+
+def _rms_check(what, H, **tensors):
+    """bf16 [rows, H] dense 16-byte-aligned activations (fp32 for names ending in '32')."""
+    if H not in RMS_FAST_WIDTHS:
+        raise InvalidArgumentError("%s: width %d is not one of %s" % (what, H, RMS_FAST_WIDTHS))
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        want = torch.float32 if name.endswith("32") else torch.bfloat16
+        if t.dtype != want or not t.is_contiguous() or t.data_ptr() % 16:
+            raise InvalidArgumentError("%s: %s must be a contiguous 16-byte-aligned %s tensor (got %s, strides %s, "
+                                       "address %% 16 = %d)" % (what, name.rstrip("32"), want, t.dtype, tuple(t.stride()),
+                                                                t.data_ptr() % 16))
+        if want == torch.bfloat16 and (t.dim() != 2 or t.shape[1] != H):
+            raise InvalidArgumentError("%s: %s must be [rows, %d], got %s" % (what, name, H, tuple(t.shape)))
+
+
+def rmsnorm_fwd(x, gamma, *, res=None, eps=1e-6, p_in=0.0, site_in=0, p_out=0.0, site_out=0, rng=None, save_s=True,
+                out=None, s_out=None, rstd=None):
+    """y = drop_out(s * rstd * gamma), s = res + drop_in(x) rounded to bf16, rstd = rsqrt(mean(s^2) + eps):
+    the residual / dropout frame of layernorm_fwd with one statistic. x, res: bf16 [rows, H], H in
+    RMS_FAST_WIDTHS; gamma fp32 [H]. Returns (y, s, rstd); s is x itself when there is neither a
+    residual nor an input dropout."""
+    if x.dim() != 2:
+        raise InvalidArgumentError("rmsnorm_fwd: x must be [rows, H], got %s" % (tuple(x.shape),))
+    rows, H = x.shape
+    dev = x.device
+    out = out if out is not None else torch.empty_like(x)
+    need_s = save_s and (res is not None or p_in > 0)
+    s_out = s_out if s_out is not None else (torch.empty_like(x) if need_s else None)
+    rstd = rstd if rstd is not None else torch.empty(rows, dtype=torch.float32, device=dev)
+    _rms_check("rmsnorm_fwd", H, x=x, res=res, out=out, s_out=s_out, gamma32=gamma)
+    if gamma.numel() != H or rstd.dtype != torch.float32 or rstd.numel() != rows or not rstd.is_contiguous():
+        raise InvalidArgumentError("rmsnorm_fwd: gamma must be fp32 [%d] and rstd fp32 [%d]" % (H, rows))
+    if (p_in > 0 or p_out > 0) and rng is None:
+        raise InvalidArgumentError("rmsnorm_fwd: dropout needs rng")
+    _lib.call("ttdk_rms_fwd", x.data_ptr(), _p(res), _p(s_out), out.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+              rows, H, float(eps), float(p_in), int(site_in), float(p_out), int(site_out),
+              _p(rng.t if rng is not None else None), _s())
+    return out, (s_out if s_out is not None else x), rstd
+
+
+def rmsnorm_bwd_workspace(rows, H, device):
+    nb = _lib.query("ttdk_rms_bwd_num_blocks", rows)
+    return torch.empty((nb, H), dtype=torch.float32, device=device)
+
+
+def rmsnorm_bwd(dy, s, rstd, gamma, dgamma, *, ds_out=None, want_dx=False, accumulate=False, p_in=0.0, site_in=0,
+                p_out=0.0, site_out=0, rng=None, work=None, dx_out=None):
+    """Backward of rmsnorm_fwd with the same dropouts: ds = dL/ds (the residual branch), dx = ds through
+    the input dropout (want_dx), dgamma fp32 [H] written or added to (accumulate). dgamma is summed
+    in a fixed order (no atomics). work: rmsnorm_bwd_workspace(rows, H)."""
+    if dy.dim() != 2:
+        raise InvalidArgumentError("rmsnorm_bwd: dy must be [rows, H], got %s" % (tuple(dy.shape),))
+    rows, H = dy.shape
+    ds_out = ds_out if ds_out is not None else torch.empty_like(dy)
+    if want_dx and dx_out is None:
+        dx_out = torch.empty_like(dy)
+    if H in RMS_FAST_WIDTHS:
+        nb = _lib.query("ttdk_rms_bwd_num_blocks", rows)
+        if work is None:
+            work = torch.empty((nb, H), dtype=torch.float32, device=dy.device)
+        elif work.dtype != torch.float32 or work.numel() < nb * H or not work.is_contiguous():
+            raise InvalidArgumentError("rmsnorm_bwd: workspace must be contiguous fp32 with >= %d x %d elements "
+                                       "(rmsnorm_bwd_workspace), got %s %s" % (nb, H, work.dtype, tuple(work.shape)))
+    _rms_check("rmsnorm_bwd", H, dy=dy, s=s, ds_out=ds_out, dx_out=dx_out if want_dx else None, gamma32=gamma,
+               dgamma32=dgamma, work32=work, rstd32=rstd)
+    if gamma.numel() != H or dgamma.numel() != H or rstd.numel() != rows:
+        raise InvalidArgumentError("rmsnorm_bwd: gamma / dgamma must be fp32 [%d] and rstd fp32 [%d]" % (H, rows))
+    if (p_in > 0 or p_out > 0) and rng is None:
+        raise InvalidArgumentError("rmsnorm_bwd: dropout needs rng")
+    _lib.call("ttdk_rms_bwd", dy.data_ptr(), s.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), ds_out.data_ptr(),
+              _p(dx_out if want_dx else None), work.data_ptr(), dgamma.data_ptr(), int(accumulate), rows, H,
+              float(p_in), int(site_in), float(p_out), int(site_out), _p(rng.t if rng is not None else None), _s())
+    return ds_out, (dx_out if want_dx else None)
+
+
+# ------------------------------------------------------------------ SwiGLU (rmsnorm_glu.hip)
+_GLU_DT = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def _glu_view(what, name, t, width):
+    if t.dim() != 2 or t.shape[1] != width or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < width):
+        raise InvalidArgumentError("%s: %s must be a 2-D [rows, %d] view with unit column stride and row stride >= "
+                                   "its width, got shape %s strides %s" % (what, name, width, tuple(t.shape),
+                                                                           tuple(t.stride())))
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def swiglu_fwd(x2, out=None):
+    """h = silu(x2[:, :I]) * x2[:, I:] for x2 [rows, 2I] (gate columns first), bf16 or fp32. x2 and out
+    are 2-D views with unit column stride, each with its own row stride (row-padded column views);
+    16-byte accesses when I, the strides and the addresses allow, a scalar kernel otherwise."""
+    if x2.dtype not in _GLU_DT:
+        raise InvalidArgumentError("swiglu_fwd takes float32 / bfloat16, got %s" % x2.dtype)
+    if x2.dim() != 2 or x2.shape[1] % 2 or x2.shape[1] == 0:
+        raise InvalidArgumentError("swiglu_fwd: x2 must be [rows, 2I], got %s" % (tuple(x2.shape),))
+    rows, I2 = x2.shape
+    Iw = I2 // 2
+    _glu_view("swiglu_fwd", "x2", x2, I2)
+    if out is None:
+        out = torch.empty((rows, Iw), dtype=x2.dtype, device=x2.device)
+    if out.dtype != x2.dtype or out.shape[0] != rows:
+        raise InvalidArgumentError("swiglu_fwd: out must be %s [%d, %d]" % (x2.dtype, rows, Iw))
+    _glu_view("swiglu_fwd", "out", out, Iw)
+    _lib.call("ttdk_swiglu_fwd", x2.data_ptr(), _ld(x2), out.data_ptr(), _ld(out), _GLU_DT[x2.dtype], rows, Iw, _s())
+    return out
+
+
+def swiglu_bwd(dh, x2, out=None):
+    """dx2 = [da | db] of swiglu_fwd from dh [rows, I] and the forward's input x2 [rows, 2I]. out may be
+    x2 itself (in place: every work item reads its gate / value pair before it writes)."""
+    if x2.dtype not in _GLU_DT or dh.dtype != x2.dtype:
+        raise InvalidArgumentError("swiglu_bwd takes float32 / bfloat16 tensors of one dtype, got %s and %s"
+                                   % (dh.dtype, x2.dtype))
+    if x2.dim() != 2 or x2.shape[1] % 2 or x2.shape[1] == 0:
+        raise InvalidArgumentError("swiglu_bwd: x2 must be [rows, 2I], got %s" % (tuple(x2.shape),))
+    rows, I2 = x2.shape
+    Iw = I2 // 2
+    _glu_view("swiglu_bwd", "x2", x2, I2)
+    _glu_view("swiglu_bwd", "dh", dh, Iw)
+    if dh.shape[0] != rows:
+        raise InvalidArgumentError("swiglu_bwd: dh has %d rows, x2 %d" % (dh.shape[0], rows))
+    if out is None:
+        out = torch.empty((rows, I2), dtype=x2.dtype, device=x2.device)
+    if out.dtype != x2.dtype or out.shape[0] != rows:
+        raise InvalidArgumentError("swiglu_bwd: out must be %s [%d, %d]" % (x2.dtype, rows, I2))
+    _glu_view("swiglu_bwd", "out", out, I2)
+    _lib.call("ttdk_swiglu_bwd", dh.data_ptr(), _ld(dh), x2.data_ptr(), _ld(x2), out.data_ptr(), _ld(out),
+              _GLU_DT[x2.dtype], rows, Iw, _s())
+    return out
+
+
+def swiglu_max_threads():
+    """Threads the capped SwiGLU grid launches; more work items than this are grid-strided."""
+    return _lib.query("ttdk_swiglu_max_threads")
 
 
 # ------------------------------------------------------------------ embeddings / rows
