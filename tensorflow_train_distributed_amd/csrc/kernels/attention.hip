@@ -8,7 +8,10 @@
 // are fp32 [B*H][S]. Scores live in the log2 domain: s2 = (q.k) * log2(e)/sqrt(64),
 // P = exp2(s2 - lse2).
 //
-// Options: per-batch key lengths (keys >= len masked), causal masking (query q attends keys
+// Options: per-batch key lengths (keys >= len masked), banded masks (BAND: every query row attends
+// one contiguous key range — packed documents, sliding windows, causal and the key length folded
+// into a table that ttdk_attn_band builds; only the tiles of a block's range are streamed:
+// profiles/attn_band_bench.txt), causal masking (query q attends keys
 // k <= q; fwd, bwd_q and bwd_kv skip the tiles above the diagonal: 20 of 32 at S = 512), and
 // attention-probability dropout whose keep mask is a counter hash of (seed, step, site,
 // (b*H+h, q, key)) — regenerated identically in both backward kernels, never stored; the hash
@@ -119,6 +122,64 @@ struct AttnParams {
   // (last, so that the fields above keep their kernarg offsets)
   int Hk, G;           // key/value heads and G = H / Hk query heads per key/value head; Hk == H,
                        // G == 1 unless grouped-query attention
+  // BAND only: the table of ttdk_attn_band
+  const int4* band_tok;  // [B][S] {klo, khi, qlo, qhi}: keys [klo, khi) of a query, queries [qlo, qhi) of a key
+  const int4* band_blk;  // [B][S/128] {kt0, kt1, qt0, qt1}: the 64-row tiles a query / key block streams
+};
+
+// BAND: a wave's 32 rows are rows i16 and 16 + i16 of every 16-lane group; min / max over them as
+// a wave-uniform (scalar) value.
+__device__ __forceinline__ int rows_min(int a, int b) {
+  int x = min(a, b);
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) x = min(x, __shfl_xor(x, o, 64));
+  return __builtin_amdgcn_readfirstlane(x);
+}
+__device__ __forceinline__ int rows_max(int a, int b) {
+  int x = max(a, b);
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) x = max(x, __shfl_xor(x, o, 64));
+  return __builtin_amdgcn_readfirstlane(x);
+}
+
+// BAND: the ranges of this lane's two rows (row0 + i16 and row0 + 16 + i16 — queries in fwd and
+// bwd_q, KEYS in bwd_kv), the union and the intersection of the ranges of the wave's 32 rows, and
+// the tile range of the 128-row block.
+struct BandRows {
+  int lo[2], w[2];         // the range's first index and its length (< 0: empty)
+  int ulo, uhi, ilo, ihi;  // wave-uniform
+  int t0, t1;              // block-uniform
+  // lo / w alone (bwd_kv reads them again in every masked tile and at the store, which is cheaper
+  // than four more registers live across its loop)
+  template <bool KEYS>
+  __device__ __forceinline__ void rows(const AttnParams& P, int b, int row0, int i16) {
+    const int4* rp = P.band_tok + static_cast<long long>(b) * P.S + row0 + i16;
+    const int2 r0 = reinterpret_cast<const int2*>(rp)[KEYS ? 1 : 0];
+    const int2 r1 = reinterpret_cast<const int2*>(rp + 16)[KEYS ? 1 : 0];
+    lo[0] = r0.x;
+    lo[1] = r1.x;
+    w[0] = r0.y - r0.x;
+    w[1] = r1.y - r1.x;
+  }
+  template <bool KEYS>
+  __device__ __forceinline__ void init(const AttnParams& P, int b, int blk, int row0, int i16) {
+    const int4 bk = P.band_blk[b * (P.S / QBLK) + blk];
+    t0 = KEYS ? bk.z : bk.x;
+    t1 = KEYS ? bk.w : bk.y;
+    rows<KEYS>(P, b, row0, i16);
+    ulo = rows_min(lo[0], lo[1]);
+    uhi = rows_max(lo[0] + w[0], lo[1] + w[1]);
+    ilo = rows_max(lo[0], lo[1]);
+    ihi = rows_min(lo[0] + w[0], lo[1] + w[1]);
+  }
+  // the tile of n indices from base: outside every row's range | inside every row's range
+  __device__ __forceinline__ bool skip(int base, int n) const { return base >= uhi || base + n <= ulo; }
+  __device__ __forceinline__ bool full(int base, int n) const { return base >= ilo && base + n <= ihi; }
+  // index idx is outside the range of row r (one subtract, one unsigned compare; an empty range
+  // has lo = S, w = -S: every idx < S is outside)
+  __device__ __forceinline__ bool masked(int r, int idx) const {
+    return static_cast<unsigned>(idx - lo[r]) >= static_cast<unsigned>(w[r]);
+  }
 };
 
 __device__ __forceinline__ uint4 ldg16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
@@ -200,7 +261,14 @@ __device__ __forceinline__ int causal_block(int j, int bh, int nblk, int order, 
 // GQA (launched when Hk != H): K / V tiles from key/value head h / G; everything else as above.
 // A template parameter, not a run-time G == 1: the self-attention kernels keep their code, without
 // the integer division at the head of every workgroup's address chain.
-template <bool DROP, bool CAUSAL = false, bool GQA = false>
+//
+// BAND (never with CAUSAL; Sk == S): row q attends keys [klo, khi) of its band_tok record, which
+// folds documents, window, causal and seqlen. The block streams key tiles kt0 .. kt1 - 1 of its
+// band_blk record only. Per wave (wave-uniform, from the min / max of its 32 rows' ranges): a tile
+// outside the union of the ranges is skipped like a causal tile above the diagonal; a tile inside
+// their intersection runs no compare; any other tile masks per element, -inf before the row max.
+// A row with an empty range (klo = S, khi = 0: padding) keeps m = -inf, l = 0: O = 0, lse = -inf.
+template <bool DROP, bool CAUSAL = false, bool GQA = false, bool BAND = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int qblocks = P.S / QBLK;
@@ -212,9 +280,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int q0 = qblk * QBLK + wave * 32;
-  const int len = P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;
+  const int len = BAND ? P.Sk : P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;  // BAND: in the table
   const long long tok0 = static_cast<long long>(b) * P.S;    // query rows: Q, O, dO, dQ
   const long long tokk = static_cast<long long>(b) * P.Sk;   // key rows: K, V, dK, dV
+  BandRows band;
+  if constexpr (BAND) band.init<false>(P, b, qblk, q0, i16);
 
   bf16x8_t qf[2][2];
 #pragma unroll
@@ -238,15 +308,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
   int ntiles = (len + KT - 1) / KT;
   if constexpr (CAUSAL) ntiles = min(ntiles, 2 * qblk + 2);
-  if (ntiles > 0) {
-    lk.load(0, len);
-    lv.load(0, len);
+  int kt0 = 0;
+  if constexpr (BAND) {
+    kt0 = band.t0;
+    ntiles = band.t1;
+  }
+  if (ntiles > kt0) {
+    lk.load(kt0 * KT, len);
+    lv.load(kt0 * KT, len);
     lk.store(smem);
     lv.store(smem + TILE_BYTES);
   }
   __syncthreads();
   int cur = 0;
-  for (int kt = 0; kt < ntiles; ++kt) {
+  for (int kt = kt0; kt < ntiles; ++kt) {
     const bool nxt = kt + 1 < ntiles;
     if (nxt) {
       lk.load((kt + 1) * KT, len);
@@ -255,7 +330,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     const char* sK = smem + cur * 2 * TILE_BYTES;
     const char* sV = sK + TILE_BYTES;
     // CAUSAL: every key of the tile lies above every row of this wave (wave-uniform)
-    if (!CAUSAL || kt * KT <= q0 + 31) {
+    // BAND: the tile lies outside the range of every row of this wave (wave-uniform)
+    if (BAND ? !band.skip(kt * KT, KT) : !CAUSAL || kt * KT <= q0 + 31) {
       // ---- S^T tile: lane holds keys kb*16 + 4g + i for query qb*16 + i16
       f32x4_t s[2][4];
 #pragma unroll
@@ -269,7 +345,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
         }
       }
       const int kbase = kt * KT;
-      if (kbase + KT > len) {
+      if constexpr (BAND) {
+        if (!band.full(kbase, KT)) {
+          // (wave-uniform: some row's range ends inside the tile)
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+              for (int i = 0; i < 4; ++i)
+                if (band.masked(qb, kbase + 4 * g + kb * 16 + i)) s[qb][kb][i] = -INFINITY;
+        }
+      }
+      if (!BAND && kbase + KT > len) {
         // (block-uniform: only the last key tile of a padded sequence; the full tiles run no
         // per-element compare / select — the kernel is VALU-bound, profiles/r3_bert_*_pmc_*)
 #pragma unroll
@@ -313,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
         const bool grow = mxs > m[qb] + 8.f;
         if (__builtin_amdgcn_ballot_w64(grow) != 0) {
           float mnew = fmaxf(m[qb], mxs);
-          if constexpr (CAUSAL) mnew = grow ? mnew : m[qb];  // per row: alpha is exactly 1 elsewhere
+          if constexpr (CAUSAL || BAND) mnew = grow ? mnew : m[qb];  // per row: alpha is exactly 1 elsewhere
           alpha = fast_exp2(m[qb] - (mnew == -INFINITY ? 0.f : mnew));
           m[qb] = mnew;
 #pragma unroll
@@ -409,7 +497,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 // GQA (MODE 0 only; launched when Hk != H): the workgroup owns 128 keys of key/value head hk of
 // batch b (grid B*Hk*Sk/128; causal_block() and the XCD remap take b*Hk + hk) and runs the sweep
 // above once per query head h0 .. h0 + G - 1 of its group, h0 = hk * G, into the same dk / dv.
-template <bool DROP, int MODE = 0, bool CAUSAL = false, bool GQA = false>
+//
+// BAND (MODE 0 only, never with CAUSAL; Sk == S): key k is attended by queries [qlo, qhi) of its
+// band_tok record, fixed for the workgroup's keys. The sweep runs query tiles qt0 .. qt1 - 1 of
+// the block's band_blk record (both even: whole trips; every head of a GQA group the same range).
+// Per trip and wave (wave-uniform): both tiles inside the intersection of the 32 keys' ranges —
+// today's unmasked body; otherwise the masked form, which skips a tile outside the union of the
+// ranges and selects a score of -inf for the elements outside their key's range: P = exp2(-inf) = 0
+// and dS = 0 exactly. The query may be a padding row with lse = -inf: it is staged as +inf, so
+// nothing is computed through exp2(-inf + inf).
+template <bool DROP, int MODE = 0, bool CAUSAL = false, bool GQA = false, bool BAND = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   constexpr int BUF = 2 * TILE_BYTES + 2 * KT * 4;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -424,9 +521,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int k0 = kblk * QBLK + wave * 32;
-  const int len = P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;
+  const int len = BAND ? P.Sk : P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;  // BAND: in the table
   const long long tok0 = static_cast<long long>(b) * P.S;    // query rows: Q, O, dO, dQ
   const long long tokk = static_cast<long long>(b) * P.Sk;   // key rows: K, V, dK, dV
+  BandRows band;
+  if constexpr (BAND) band.init<true>(P, b, kblk, k0, i16);
   long long stamp[6] = {};
   if constexpr ((MODE & 8) != 0) {
     stamp[0] = __builtin_amdgcn_s_memtime();
@@ -439,7 +538,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 #pragma unroll
     for (int db = 0; db < 4; ++db) dk[kb][db] = dv[kb][db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const bool any = kblk * QBLK < len;  // block-uniform: some key of this block is valid
+  // block-uniform: some key of this block is valid (BAND: is attended by some query)
+  const bool any = BAND ? band.t0 < band.t1 : kblk * QBLK < len;
   if (any) {
     bf16x8_t kf[2][2], vf[2][2];
 #pragma unroll
@@ -464,16 +564,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     const float st_mul = tid >= KT && DROP ? 1.f / P.drop_scale : 1.f;
     float stv = 0.f;
     const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
-    const int ntiles = P.S / KT;  // query tiles; even: S is a multiple of QBLK = 2 * KT
+    // query tiles; even: S is a multiple of QBLK = 2 * KT (BAND: the sweep's end, even too)
+    const int ntiles = BAND ? band.t1 : P.S / KT;
 
     auto load = [&](int qt) {
-      lq.load(qt * KT, P.S);
-      ld.load(qt * KT, P.S);
+      // (BAND: the sweep ends at a tile the table names, inside the S rows — no partial-tile path)
+      lq.load(qt * KT, BAND ? 0x7fffffff : P.S);
+      ld.load(qt * KT, BAND ? 0x7fffffff : P.S);
       if (tid < 2 * KT) stv = st_src[qt * KT];
     };
     auto store = [&](char* nb) {
       lq.store(nb);
       ld.store(nb + TILE_BYTES);
+      // BAND: a padding row's lse2 = -inf is staged as +inf: exp2(s - lse2) = 0 for every s (see pds)
+      if constexpr (BAND) stv = tid < KT && stv == -INFINITY ? INFINITY : stv;
       if (tid < 2 * KT) reinterpret_cast<float*>(nb + 2 * TILE_BYTES)[tid] = (stv + st_add) * st_mul;
     };
     // S[q][key] and dP[q][key] for the query rows of half hq (qb = 2 hq, 2 hq + 1) of the tile
@@ -511,7 +615,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     // first query + 4g) of the lane's kb = 0 key; the score is -inf there, so P_d = 0 and dS = 0
     // exactly (masking the score, not p, also keeps this form free of spills).
     auto pds = [&](const float* sL, const uint32_t (&hq_hash)[2][4], int hq, f32x4_t (&sc)[4][2], f32x4_t (&dp)[4][2],
-                   auto diag_c, int kd) {
+                   auto diag_c, int kd, const BandRows& br) {
       constexpr bool DIAG = decltype(diag_c)::value;
       const float* sDel = sL + KT;
 #pragma unroll
@@ -524,7 +628,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 #pragma unroll
           for (int kb = 0; kb < 2; ++kb) {
             float sv = sc[qb][kb][i];
-            if constexpr (DIAG) sv = qb * 16 + i - kb * 16 < kd ? -INFINITY : sv;
+            if constexpr (DIAG && !BAND) sv = qb * 16 + i - kb * 16 < kd ? -INFINITY : sv;
+            // BAND (kd: the tile's first query + 4g): the query lies outside this key's range; the
+            // select gives p = exp2(-inf) = 0 and dS = 0 exactly — also in a padding row, whose
+            // lse2 = -inf was staged as +inf (store()), never exp2(-inf + inf)
+            if constexpr (DIAG && BAND) sv = br.masked(kb, kd + qb * 16 + i) ? -INFINITY : sv;
             const float p = fast_exp2(__builtin_fmaf(sv, P.scale_log2, -lse2));
             const float dpv = dp[qb][kb][i];
             if constexpr (DROP) {
@@ -570,14 +678,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
       constexpr int BUFI = decltype(bufi_c)::value;
       constexpr bool DIAG = decltype(diag_c)::value;
       constexpr int DV = DIAG ? 2 : 0;  // the mask's compare and select per element, per MFMA slot
-      const int kd = k0 + i16 - qt * KT - 4 * g;
+      const int kd = BAND ? qt * KT + 4 * g : k0 + i16 - qt * KT - 4 * g;
       if constexpr (!GQA) {  // always the head's next tile; the two arguments are not read
         nq = qt + 1;
         nxt = qt + 1 < ntiles;
       }
       nxt = nxt && !(MODE & 2);
       if (nxt) load(nq);
-      if (!DIAG || __builtin_amdgcn_readfirstlane(k0) <= qt * KT + KT - 1) {
+      if (!DIAG || (BAND ? !band.skip(qt * KT, KT) : __builtin_amdgcn_readfirstlane(k0) <= qt * KT + KT - 1)) {
         const char* sQ = smem + BUFI * BUF;
         const float* sL = reinterpret_cast<const float*>(sQ + 2 * TILE_BYTES);
         const uint32_t hrow = DROP ? attn_row_term(static_cast<uint32_t>(bh * P.S + qt * KT + 4 * g)) +
@@ -590,6 +698,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
         uint32_t h0[2][4] = {}, h1[2][4] = {};
         sdp(sQ, 0, sc, dp);
         hashes(hrow, 0, h0);
+        // BAND, masked form: the ranges of this lane's two keys, read again per tile (four more
+        // registers live across the loop spill)
+        BandRows br;
+        if constexpr (DIAG && BAND) br.rows<true>(P, b, k0, i16);
         __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -598,7 +710,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
         }
         __builtin_amdgcn_sched_barrier(0);
         sdp(sQ, 1, sc, dp);
-        if constexpr (!(MODE & 1)) pds(sL, h0, 0, sc, dp, diag_c, kd);
+        if constexpr (!(MODE & 1)) pds(sL, h0, 0, sc, dp, diag_c, kd, br);
         hashes(hrow, 1, h1);
         __builtin_amdgcn_sched_group_barrier(0x100, 12, 1);
 #pragma unroll
@@ -608,7 +720,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
         }
         __builtin_amdgcn_sched_barrier(0);
         pv(sQ, 0, sc, dp);
-        if constexpr (!(MODE & 1)) pds(sL, h1, 1, sc, dp, diag_c, kd);
+        if constexpr (!(MODE & 1)) pds(sL, h1, 1, sc, dp, diag_c, kd, br);
         __builtin_amdgcn_sched_group_barrier(0x100, 20, 2);
         __builtin_amdgcn_sched_group_barrier(0x002, 8, 2);
 #pragma unroll
@@ -625,7 +737,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
     using std::integral_constant;
     using std::false_type;
     using std::true_type;
-    const int qt0 = CAUSAL ? 2 * kblk : 0;
+    const int qt0 = BAND ? band.t0 : CAUSAL ? 2 * kblk : 0;
+    // BAND, wave-uniform: the two tiles of the trip from tile q lie inside the range of every key of
+    // this wave — the unmasked body; the waves of a workgroup may differ (each form has the trip's
+    // two barriers)
+    auto band_full = [&](int q) { return band.full(q * KT, 2 * KT); };
     load(qt0);
     store(smem);
     __syncthreads();
@@ -640,9 +756,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
         tile(qt + 1, 0, false, integral_constant<int, 1>{}, true_type{});
         qt += 2;
       }
-      for (; qt < ntiles; qt += 2) {  // ntiles - qt is even
-        tile(qt, 0, false, integral_constant<int, 0>{}, false_type{});
-        tile(qt + 1, 0, false, integral_constant<int, 1>{}, false_type{});
+      if constexpr (BAND) {
+        // runs of masked trips and runs of unmasked trips, a loop each (one loop that chooses per
+        // trip spills 200-280 bytes)
+        while (qt < ntiles) {
+          for (; qt < ntiles && !band_full(qt); qt += 2) {
+            tile(qt, 0, false, integral_constant<int, 0>{}, true_type{});
+            tile(qt + 1, 0, false, integral_constant<int, 1>{}, true_type{});
+          }
+          for (; qt < ntiles && band_full(qt); qt += 2) {
+            tile(qt, 0, false, integral_constant<int, 0>{}, false_type{});
+            tile(qt + 1, 0, false, integral_constant<int, 1>{}, false_type{});
+          }
+        }
+      } else {
+        for (; qt < ntiles; qt += 2) {  // ntiles - qt is even
+          tile(qt, 0, false, integral_constant<int, 0>{}, false_type{});
+          tile(qt + 1, 0, false, integral_constant<int, 1>{}, false_type{});
+        }
       }
     } else {
       // Grouped-query attention: the G query heads of this key/value head in head order, each
@@ -668,7 +799,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
       // (two loop shapes for one sequence of trips, chosen by the register allocation they get:
       // the causal kernels spill 104 / 248 bytes in the flat shape, the bidirectional one without
       // dropout 24 bytes in the nested shape; as written every instantiation has no scratch)
-      if constexpr (CAUSAL) {
+      if constexpr (BAND) {
+        // (runs of masked and of unmasked trips, a loop each, as above. Without dropout that shape —
+        // and every other one tried — spills 12 bytes or more, so that one instantiation runs the
+        // masked body on every trip: the compare on the unmasked tiles too, but no scratch)
+        if constexpr (!DROP) {
+          do {
+            if (trip(true_type{})) ++bh;
+          } while (heads_left > 0);
+        } else {
+          do {
+            bool last = false;
+            while (!last && !band_full(qt)) last = trip(true_type{});
+            while (!last && band_full(qt)) last = trip(false_type{});
+            while (!last) last = trip(true_type{});
+            ++bh;
+          } while (heads_left > 0);
+        }
+      } else if constexpr (CAUSAL) {
         do {
           bool last = trip(true_type{});
           while (!last) last = trip(false_type{});
@@ -684,12 +832,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
   }
   // store dK (scaled by 1/sqrt(D)) and dV: lane holds key kb*16 + i16, d = db*16 + 4g + i; keys
   // >= len get zeros (their accumulators saw unmasked probabilities)
+  if constexpr (BAND) band.rows<true>(P, b, k0, i16);
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     const long long row = tokk + k0 + kb * 16 + i16;
     bf16_t* pk = P.out + row * P.ld_out + hk * D + 4 * g;
     bf16_t* pv = P.out2 + row * P.ld_out2 + hk * D + 4 * g;
-    const bool valid = k0 + kb * 16 + i16 < len;
+    const bool valid = BAND ? band.w[kb] > 0 : k0 + kb * 16 + i16 < len;
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
       const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
@@ -717,7 +866,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(AttnParams P) {
 // CAUSAL: as the forward — key tiles kt <= 2 qblk + 1 only; per wave a tile runs full, diagonal
 // (score -inf where key > query, before the exp2: P = 0 and dS = 0 exactly) or skipped.
 // GQA: as the forward — K / V tiles from key/value head h / G.
-template <bool DROP, bool CAUSAL = false, bool GQA = false>
+// BAND: as the forward — key tiles kt0 .. kt1 - 1 of the block's record; per wave a tile runs full
+// (inside every row's range), masked or skipped (outside every row's range). A masked element gets
+// a score of -inf by select, so P = 0 and dS = 0 exactly; a padding row's lse = -inf is read as +inf.
+template <bool DROP, bool CAUSAL = false, bool GQA = false, bool BAND = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int qblocks = P.S / QBLK;
@@ -729,9 +881,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i16 = lane & 15;
   const int q0 = qblk * QBLK + wave * 32;
-  const int len = P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;
+  const int len = BAND ? P.Sk : P.seqlen ? min(P.seqlen[b], P.Sk) : P.Sk;  // BAND: in the table
   const long long tok0 = static_cast<long long>(b) * P.S;    // query rows: Q, O, dO, dQ
   const long long tokk = static_cast<long long>(b) * P.Sk;   // key rows: K, V, dK, dV
+  BandRows band;
+  if constexpr (BAND) band.init<false>(P, b, qblk, q0, i16);
 
   bf16x8_t qf[2][2], df[2][2];
   float lse2[2], del[2];
@@ -754,6 +908,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     del[qb] = acc;
     const long long srow = static_cast<long long>(bh) * P.S + q0 + qb * 16 + i16;
     lse2[qb] = P.lse[srow];
+    // BAND: a padding row (lse2 = -inf; all its keys masked, s = -inf) takes +inf here, so that
+    // exp2(s - lse2) is exp2(-inf) = 0 and dS = 0 exactly, never exp2(-inf + inf)
+    if constexpr (BAND) lse2[qb] = lse2[qb] == -INFINITY ? INFINITY : lse2[qb];
     if (g == 0) P.delta[srow] = acc;
     if constexpr (DROP) {
       // dS = P * (keep * dP / (1-p) - delta) = P_d' * dP - P' * (delta * (1-p)) with P' = P / (1-p)
@@ -775,9 +932,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
   const uint32_t key = DROP ? drop_key(P.rng, P.site) : 0u;
   int ntiles = (len + KT - 1) / KT;
   if constexpr (CAUSAL) ntiles = min(ntiles, 2 * qblk + 2);
-  if (ntiles > 0) {
-    lk.load(0, len);
-    lv.load(0, len);
+  int kt0 = 0;
+  if constexpr (BAND) {
+    kt0 = band.t0;
+    ntiles = band.t1;
+  }
+  if (ntiles > kt0) {
+    lk.load(kt0 * KT, len);
+    lv.load(kt0 * KT, len);
     lk.store(smem);
     lv.store(smem + TILE_BYTES);
   }
@@ -826,7 +988,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float sv = sc[qb][kb][i];
-          if constexpr (DIAG) sv = kb * 16 + i - qb * 16 > qd ? -INFINITY : sv;
+          if constexpr (DIAG && !BAND) sv = kb * 16 + i - qb * 16 > qd ? -INFINITY : sv;
+          // BAND (qd: the tile's first key + 4g): the key lies outside this row's range
+          if constexpr (DIAG && BAND) sv = band.masked(qb, qd + kb * 16 + i) ? -INFINITY : sv;
           const float p = fast_exp2(__builtin_fmaf(sv, P.scale_log2, -lse2[qb]));
           const float dpv = dp[qb][kb][i];
           if constexpr (DROP) {
@@ -873,7 +1037,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     }
     const char* sK = smem + cur * 2 * TILE_BYTES;
     const int kbase = kt * KT;
-    const int qd = q0 + i16 - kbase - 4 * g;
+    const int qd = BAND ? kbase + 4 * g : q0 + i16 - kbase - 4 * g;
     uint32_t h0[2][4] = {}, h1[2][4] = {};
     sdp(sK, 0, sc, dp);
     hashes(kbase, 0, h0);
@@ -906,8 +1070,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(AttnParams P) {
     __syncthreads();
     cur ^= 1;
   };
-  for (int kt = 0; kt < ntiles; ++kt) {
-    if constexpr (CAUSAL) {
+  for (int kt = kt0; kt < ntiles; ++kt) {
+    if constexpr (BAND) {
+      // wave-uniform: outside every row's range | some row's range ends inside the tile
+      if (band.skip(kt * KT, KT)) tile(kt, std::integral_constant<int, 2>{});
+      else if (!band.full(kt * KT, KT)) tile(kt, std::integral_constant<int, 1>{});
+      else tile(kt, std::integral_constant<int, 0>{});
+    } else if constexpr (CAUSAL) {
       // wave-uniform: all keys above all of the wave's rows | the tile crosses its diagonal
       if (kt * KT > q0 + 31) tile(kt, std::integral_constant<int, 2>{});
       else if (kt * KT + KT - 1 > q0) tile(kt, std::integral_constant<int, 1>{});
@@ -1144,6 +1313,74 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_fused_kernel(AttnParams P
   }
 }
 
+// ------------------------------------------------------------------------------ band table
+// One workgroup per batch row builds the BAND kernels' table (AttnParams::band_tok / band_blk) from
+// segment ids (a token attends its own maximal run of equal ids; id < 0: padding), the key length,
+// the window (wl / wr < 0: unbounded) — causal is wr = 0 by now. Linear in S: thread t owns a
+// contiguous chunk of tokens; the run start of a token is the last run boundary at or before it,
+// the run end the first boundary after it — a carry across the chunks (through LDS) and one pass
+// over the chunk each way. Then wave w reduces the records of blocks w, w + 4, ... to tile ranges.
+__global__ __launch_bounds__(256) void attn_band_kernel(const int* ids, const int* seqlen, int S, int wl, int wr,
+                                                        int4* tok, int4* blk) {
+  __shared__ int s_last[256], s_first[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int per = (S + 255) / 256;
+  const int c0 = min(t * per, S), c1 = min(c0 + per, S);
+  const int* id = ids ? ids + static_cast<long long>(b) * S : nullptr;
+  const int len = seqlen ? min(max(seqlen[b], 0), S) : S;
+  int4* row = tok + static_cast<long long>(b) * S;
+  auto starts = [&](int s) { return s == 0 || (id != nullptr && id[s] != id[s - 1]); };
+  int last = 0, first = S;  // the chunk's last and first run boundary
+  for (int s = c1 - 1; s >= c0; --s)
+    if (starts(s)) {
+      first = s;
+      last = max(last, s);
+    }
+  s_last[t] = last;
+  s_first[t] = first;
+  __syncthreads();
+  int rs = 0, nx = S;  // the run start carried into the chunk, the first boundary after it
+  for (int u = 0; u < t; ++u) rs = max(rs, s_last[u]);
+  for (int u = t + 1; u < 256; ++u) nx = min(nx, s_first[u]);
+  for (int s = c0; s < c1; ++s) {
+    if (starts(s)) rs = s;
+    row[s].x = rs;
+  }
+  for (int s = c1 - 1; s >= c0; --s) {
+    const int r0 = row[s].x, r1 = nx;  // the run [r0, r1) of token s
+    if (starts(s)) nx = s;
+    int klo = r0, khi = min(r1, len), qlo = r0, qhi = r1;
+    if (wl >= 0) {
+      klo = max(klo, s - wl);
+      qhi = min(qhi, s + wl + 1);
+    }
+    if (wr >= 0) {
+      khi = min(khi, s + wr + 1);
+      qlo = max(qlo, s - wr);
+    }
+    const bool pad = id != nullptr && id[s] < 0;
+    const bool ek = pad || klo >= khi, eq = pad || s >= len || qlo >= qhi;
+    row[s] = make_int4(ek ? S : klo, ek ? 0 : khi, eq ? S : qlo, eq ? 0 : qhi);
+  }
+  __syncthreads();  // the records of this row, written by this workgroup, are read back below
+  const int lane = t & 63, nblk = S / QBLK;
+  for (int j = t >> 6; j < nblk; j += 4) {
+    const int4 a = row[j * QBLK + lane], c = row[j * QBLK + 64 + lane];
+    int klo = min(a.x, c.x), khi = max(a.y, c.y), qlo = min(a.z, c.z), qhi = max(a.w, c.w);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      klo = min(klo, __shfl_xor(klo, o, 64));
+      khi = max(khi, __shfl_xor(khi, o, 64));
+      qlo = min(qlo, __shfl_xor(qlo, o, 64));
+      qhi = max(qhi, __shfl_xor(qhi, o, 64));
+    }
+    // the key-side sweep in whole trips of two tiles: first tile even, end even
+    if (lane == 0)
+      blk[b * nblk + j] = make_int4(khi > 0 ? klo / KT : 0, (khi + KT - 1) / KT, qhi > 0 ? (qlo / KT) & ~1 : 0,
+                                    (qhi + QBLK - 1) / QBLK * 2);
+  }
+}
+
 AttnParams make_params(int B, int H, int Hk, int S, int Sk, const int* seqlen, float p_drop, const long long* rng,
                        uint32_t site) {
   AttnParams P{};
@@ -1208,6 +1445,19 @@ constexpr AttnKernel kBwdKv[2][2][2] = {
      {attn_bwd_kv_kernel<false, 0, true, false>, attn_bwd_kv_kernel<true, 0, true, false>}},
     {{attn_bwd_kv_kernel<false, 0, false, true>, attn_bwd_kv_kernel<true, 0, false, true>},
      {attn_bwd_kv_kernel<false, 0, true, true>, attn_bwd_kv_kernel<true, 0, true, true>}}};
+
+// The BAND instantiations, indexed [gqa][drop]: causal and the key length are in the table.
+constexpr AttnKernel kFwdBand[2][2] = {
+    {attn_fwd_kernel<false, false, false, true>, attn_fwd_kernel<true, false, false, true>},
+    {attn_fwd_kernel<false, false, true, true>, attn_fwd_kernel<true, false, true, true>}};
+
+constexpr AttnKernel kBwdQBand[2][2] = {
+    {attn_bwd_q_kernel<false, false, false, true>, attn_bwd_q_kernel<true, false, false, true>},
+    {attn_bwd_q_kernel<false, false, true, true>, attn_bwd_q_kernel<true, false, true, true>}};
+
+constexpr AttnKernel kBwdKvBand[2][2] = {
+    {attn_bwd_kv_kernel<false, 0, false, false, true>, attn_bwd_kv_kernel<true, 0, false, false, true>},
+    {attn_bwd_kv_kernel<false, 0, false, true, true>, attn_bwd_kv_kernel<true, 0, false, true, true>}};
 
 // TTD_ATTN_KV_DIAG=<mode>: the diagnostic forms of bwd_kv (MODE above). They are self-attention
 // dropout kernels: honoured only for Hk == H, non-causal, p_drop > 0; any other value runs MODE 0.
@@ -1325,5 +1575,70 @@ TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, l
       if (d.mode == kv_diag()) kv = d.kernel;
   }
   hipLaunchKernelGGL(kv, dim3(B * Hk * (Sk / QBLK)), dim3(256), 0, st, P);
+  return hipGetLastError();
+}
+
+// ---- banded masks (packed documents, sliding windows, causal, key length: attn_band_kernel)
+// The table: int32 [4*B*S + 4*B*(S/128)], 16-byte aligned — per token {klo, khi, qlo, qhi}, then per
+// 128-token block {kt0, kt1, qt0, qt1}. segment_ids int32 [B][S] or null, seqlen [B] or null,
+// window_left / window_right < 0: unbounded; causal clamps the right side to 0. One launch on st,
+// no allocation, no host synchronisation: it can be captured. Built once per step and shared by
+// every layer's forward and backward.
+TTDK_EXPORT int ttdk_attn_band(const int* segment_ids, const int* seqlen, int B, int S, int window_left,
+                               int window_right, int causal, int* table, hipStream_t st) {
+  if (B <= 0 || S <= 0 || S % QBLK || table == nullptr || (reinterpret_cast<uintptr_t>(table) & 15))
+    return hipErrorInvalidValue;
+  const int wl = window_left < 0 ? -1 : min(window_left, S);
+  const int wr = causal ? 0 : window_right < 0 ? -1 : min(window_right, S);
+  int4* tok = reinterpret_cast<int4*>(table);
+  hipLaunchKernelGGL(attn_band_kernel, dim3(B), dim3(256), 0, st, segment_ids, seqlen, S, wl, wr, tok,
+                     tok + static_cast<long long>(B) * S);
+  return hipGetLastError();
+}
+
+namespace {
+bool band_params(AttnParams& P, const int* band, int B, int Sq, int Sk) {
+  if (band == nullptr || (reinterpret_cast<uintptr_t>(band) & 15) || Sq != Sk) return false;
+  P.band_tok = reinterpret_cast<const int4*>(band);
+  P.band_blk = P.band_tok + static_cast<long long>(B) * Sq;
+  return true;
+}
+}  // namespace
+
+// ttdk_attn_fwd with the table of ttdk_attn_band in the place of seqlen and causal (both are in the
+// table). Self-attention only: Sq != Sk is refused.
+TTDK_EXPORT int ttdk_attn_band_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                   long long ldv, bf16_t* o, long long ldo, float* lse, const int* band, int B, int H,
+                                   int Hk, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
+                                   hipStream_t st) {
+  if (!args_ok(H, Hk, Sq, Sk, 1, p_drop, rng, ldq | ldk | ldv | ldo, {q, k, v, o})) return hipErrorInvalidValue;
+  AttnParams P = make_params(B, H, Hk, Sq, Sk, nullptr, p_drop, rng, site);
+  if (!band_params(P, band, B, Sq, Sk)) return hipErrorInvalidValue;
+  P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
+  P.out = o; P.ld_out = ldo; P.lse = lse;
+  hipLaunchKernelGGL(kFwdBand[Hk != H][p_drop > 0.f], dim3(B * H * (Sq / QBLK)), dim3(256), 0, st, P);
+  return hipGetLastError();
+}
+
+// The backward of ttdk_attn_band_fwd: always the split kernels (the fused backward has no band
+// form), bwd_q then bwd_kv as in ttdk_attn_bwd.
+TTDK_EXPORT int ttdk_attn_band_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+                                   long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
+                                   const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk,
+                                   long long lddk, bf16_t* dv, long long lddv, const int* band, int B, int H, int Hk,
+                                   int Sq, int Sk, float p_drop, const long long* rng, unsigned site, hipStream_t st) {
+  if (!args_ok(H, Hk, Sq, Sk, 1, p_drop, rng, ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv, {q, k, v, o, dout}))
+    return hipErrorInvalidValue;
+  const bool gqa = Hk != H, drop = p_drop > 0.f;
+  AttnParams P = make_params(B, H, Hk, Sq, Sk, nullptr, p_drop, rng, site);
+  if (!band_params(P, band, B, Sq, Sk)) return hipErrorInvalidValue;
+  P.q = q; P.k = k; P.v = v; P.o = o; P.dout = dout;
+  P.ldq = ldq; P.ldk = ldk; P.ldv = ldv; P.ldo = ldo; P.lddo = lddo;
+  P.lse = const_cast<float*>(lse);
+  P.delta = delta;
+  P.out = dq; P.ld_out = lddq; P.out2 = nullptr;
+  hipLaunchKernelGGL(kBwdQBand[gqa][drop], dim3(B * H * (Sq / QBLK)), dim3(256), 0, st, P);
+  P.out = dk; P.ld_out = lddk; P.out2 = dv; P.ld_out2 = lddv;
+  hipLaunchKernelGGL(kBwdKvBand[gqa][drop], dim3(B * Hk * (Sk / QBLK)), dim3(256), 0, st, P);
   return hipGetLastError();
 }

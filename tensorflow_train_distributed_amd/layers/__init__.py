@@ -377,12 +377,22 @@ class MultiHeadAttention(Layer):
     [q | k] column slice of the fused projection (num_heads + num_kv_heads heads, one kernel
     launch on the GPU); in cross-attention the queries at positions 0..S-1 and the keys at
     0..Sk-1. It adds no variable and composes with use_causal_mask, seqlen, num_kv_heads and
-    dropout."""
+    dropout.
+    window=(left, right) is sliding-window (local) self-attention: position q attends positions
+    q - left .. q + right, None on a side for no bound. call(..., segment_ids=) takes int32
+    [B, S] document ids of a packed row: a token attends its own maximal run of equal ids only, a
+    negative id is padding (zero output row, zero gradients) — ttd.nn.attention has the details.
+    Neither adds a variable; both compose with use_causal_mask, seqlen, num_kv_heads and rotary, and
+    both need value=None. Rotary angles enter the scores through position differences only, so the
+    documents of a packed row need no per-document position restart with rotary=True."""
     _default_name = "multi_head_attention"
 
     def __init__(self, num_heads, key_dim=64, dropout=0.0, num_kv_heads=None, rotary=False, rotary_base=10000.0,
-                 name=None):
+                 window=None, name=None):
         super().__init__(name)
+        from ..ops.transformer import _band_window
+        _band_window(window)  # raises on a malformed window
+        self.window = None if window is None else tuple(window)
         self.num_heads, self.key_dim, self.dropout = int(num_heads), int(key_dim), float(dropout)
         self.rotary, self.rotary_base = bool(rotary), float(rotary_base)
         self.num_kv_heads = self.num_heads if num_kv_heads is None else int(num_kv_heads)
@@ -402,7 +412,7 @@ class MultiHeadAttention(Layer):
         self.add_weight("output/bias", (D,), "zeros", attr="out_bias")
         super().build(input_shape)
 
-    def call(self, x, value=None, seqlen=None, training=True, use_causal_mask=False, **kw):
+    def call(self, x, value=None, seqlen=None, training=True, use_causal_mask=False, segment_ids=None, **kw):
         inner = self.num_heads * self.key_dim
         inner_kv = self.num_kv_heads * self.key_dim
         if value is None:
@@ -424,9 +434,9 @@ class MultiHeadAttention(Layer):
             if self.rotary:  # each side by its own positions: 0..S-1 and 0..Sk-1
                 q = N.rotary_embedding(q, self.num_heads, self.rotary_base)
                 k = N.rotary_embedding(k, self.num_kv_heads, self.rotary_base)
-        a =N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
+        a = N.attention(q.contiguous(), k.contiguous(), v.contiguous(), self.num_heads,
                         self.dropout if training else 0.0, seqlen=seqlen, causal=use_causal_mask,
-                        num_kv_heads=self.num_kv_heads)
+                        num_kv_heads=self.num_kv_heads, segment_ids=segment_ids, window=self.window)
         return N.dense(a, self.out_kernel, self.out_bias)
 
 

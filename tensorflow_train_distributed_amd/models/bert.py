@@ -71,6 +71,13 @@ class BertConfig:
     # projection and the [tokens, I] unit for the backward: 3 * tokens * I elements per layer
     # against 2 * tokens * I without the flag.
     gated_ffn: bool = False
+    # sliding-window (local) self-attention: None, or (left, right) — position q attends positions
+    # q - left .. q + right, None on a side for no bound (ops.transformer.attention_band; the BAND
+    # attention kernels stream only the key tiles inside the window). Intersects with causal and
+    # with the batch's seqlen; composes with rotary, rms_norm and gated_ffn. The parameter set does
+    # NOT change with the flag. (Packed documents are not an engine option: the learned position
+    # table and the NSP rows are per sequence.)
+    attention_window: Optional[tuple] = None
 
     @property
     def vocab_padded(self) -> int:
@@ -455,6 +462,15 @@ class BertPretraining:
         ids = batch.input_ids.reshape(-1)
         tt = batch.token_type_ids.reshape(-1)
         seqlen = batch.seqlen
+        # sliding window: one band table per step (window, causal and the key lengths folded in), in
+        # a per-shape buffer, shared by every layer's attention forward and backward
+        band = None
+        if c.attention_window is not None:
+            bufs = self.__dict__.setdefault("_band_bufs", {})
+            if (B, S) not in bufs:
+                bufs[(B, S)] = torch.empty(T.attention_band_ints(B, S), dtype=torch.int32, device=dev)
+            band = T.attention_band(None, seqlen, c.attention_window, c.causal, B, S, out=bufs[(B, S)])
+        attn_mask = dict(band=band) if band is not None else dict(seqlen=seqlen, causal=c.causal)
         # MLM rows b*S + positions[b, p] and CLS rows b*S, formed inside the gather / scatter kernels
         pos_idx = batch.masked_lm_positions.reshape(-1)
         if pos_idx.dtype != torch.int32 or not pos_idx.is_contiguous():
@@ -490,8 +506,8 @@ class BertPretraining:
             lse = torch.empty((B * NH, S), dtype=torch.float32, device=dev)
             if c.rotary:  # q and k in place; the rotated qkv is what the attention backward reads too
                 T.rope(qkv, qkv, self.rope_table, S, 2 * NH)
-            T.attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, lse, B, NH, S, seqlen=seqlen,
-                            p_drop=ad, rng=rng, site=site(l, 0), causal=c.causal)
+            T.attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, lse, B, NH, S, p_drop=ad, rng=rng,
+                            site=site(l, 0), **attn_mask)
             nb = self._ln(l, "attention/output/dense/bias")
             proj = self._plain(ao, P.c[self._ln(l, "attention/output/dense/kernel")], P.var[nb], P.c[nb])
             y1, s1, m1, r1 = norm_fwd(proj, self._ln(l, "attention/output/LayerNorm"), res=x, p_in=hd,
@@ -620,8 +636,8 @@ class BertPretraining:
             del dproj
             dqkv = torch.empty((Tk, 3 * H), dtype=bf, device=dev)
             T.attention_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ao, dao, lse, dqkv[:, :H],
-                            dqkv[:, H:2 * H], dqkv[:, 2 * H:], B, NH, S, delta=delta, seqlen=seqlen, p_drop=ad,
-                            rng=rng, site=site(l, 0), causal=c.causal)
+                            dqkv[:, H:2 * H], dqkv[:, 2 * H:], B, NH, S, delta=delta, p_drop=ad,
+                            rng=rng, site=site(l, 0), **attn_mask)
             if c.rotary:  # gradients of the rotated q, k -> of the projection's output
                 T.rope(dqkv, dqkv, self.rope_table, S, 2 * NH, inverse=True)
             if self.ln_yield == 2:
@@ -680,6 +696,10 @@ class BertPretraining:
             ar = torch.arange(S, device=x.device)
             keymask = ar[None, :] < batch.seqlen[:, None].long()
         tri = torch.ones((S, S), dtype=torch.bool, device=x.device).tril() if c.causal else None
+        if c.attention_window is not None:  # the window as an explicit [S, S] mask, with the triangle
+            from ..nn import attention_band_mask
+            win = attention_band_mask(None, None, c.attention_window, c.causal, 1, S, x.device)[0]
+            tri = win if tri is None else tri & win
         if c.rotary:
             from ..ops.transformer import rope_table
             tab = rope_table(c.max_position_embeddings, c.rotary_base, x.device)[:S]
@@ -701,7 +721,14 @@ class BertPretraining:
                 sc = sc.masked_fill(~keymask[:, None, None, :], float("-inf"))
             if tri is not None:
                 sc = sc.masked_fill(~tri, float("-inf"))
-            a = (sc.softmax(-1) @ v).transpose(1, 2).reshape(B, S, H)
+            if c.attention_window is not None:
+                # a query past the key length by more than the window attends nothing: a zero row, as
+                # the kernels give, not softmax's NaN
+                dead = (sc == float("-inf")).all(-1, keepdim=True)
+                pr = sc.masked_fill(dead, 0.0).softmax(-1).masked_fill(dead, 0.0)
+            else:
+                pr = sc.softmax(-1)
+            a = (pr @ v).transpose(1, 2).reshape(B, S, H)
             x = ln(x + lin(a, p("attention/output/dense")), p("attention/output/LayerNorm"))
             h = lin(x, p("intermediate/dense"))
             if c.gated_ffn:  # [gate | value] columns of the fused projection

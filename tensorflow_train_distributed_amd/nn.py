@@ -792,7 +792,7 @@ def global_avg_pool(x):
 # ------------------------------------------------------------------ attention
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal, num_kv_heads):
+    def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal, num_kv_heads, band=None):
         from .ops import transformer as T
         B, S, D = q.shape
         Sk, Dk = k.shape[1], k.shape[2]  # Dk = num_kv_heads * 64: narrower than D when heads are grouped
@@ -805,27 +805,54 @@ class _Attention(torch.autograd.Function):
             rng = T.RngState(_Rng.seed, q.device)
             rng.t[1] = _Rng.offset
             _Rng.offset += 1
+        if band is not None:  # seqlen and causal are in the table
+            seqlen, causal = None, False
         T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, Sk=Sk, Hk=num_kv_heads, seqlen=seqlen, p_drop=rate,
-                        rng=rng, site=site, causal=causal)
-        ctx.save_for_backward(q2, k2, v2, o, lse, seqlen)
+                        rng=rng, site=site, causal=causal, band=band)
+        ctx.save_for_backward(q2, k2, v2, o, lse, seqlen, band)
         ctx.cfg = (B, S, Sk, D, Dk, num_heads, num_kv_heads, rate, rng, site, q.dtype, causal)
         return o.reshape(B, S, D).to(q.dtype)
 
     @staticmethod
     def backward(ctx, do):
         from .ops import transformer as T
-        q2, k2, v2, o, lse, seqlen = ctx.saved_tensors
+        q2, k2, v2, o, lse, seqlen, band = ctx.saved_tensors
         B, S, Sk, D, Dk, nh, nkv, rate, rng, site, dt, causal = ctx.cfg
         d2 = do.reshape(B * S, D).to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2)
         T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, Sk=Sk, Hk=nkv, seqlen=seqlen, p_drop=rate,
-                        rng=rng, site=site, causal=causal)
+                        rng=rng, site=site, causal=causal, band=band)
         return (dq.reshape(B, S, D).to(dt), dk.reshape(B, Sk, Dk).to(dt), dv.reshape(B, Sk, Dk).to(dt),
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
+
+
+def attention_band_mask(segment_ids, seqlen, window, causal, B, S, device):
+    """Boolean [B, S(query), S(key)] mask of the banded attention (see attention): True where the
+    query attends the key. The explicit form of the table the GPU kernels read."""
+    ar = torch.arange(S, device=device)
+    m = torch.ones((B, S, S), dtype=torch.bool, device=device)
+    if segment_ids is not None:
+        ids = segment_ids.to(device).long()
+        start = torch.ones((B, S), dtype=torch.bool, device=device)
+        start[:, 1:] = ids[:, 1:] != ids[:, :-1]
+        run = start.long().cumsum(1)  # the number of the token's maximal run of equal ids
+        valid = ids >= 0
+        m = m & (run[:, :, None] == run[:, None, :]) & valid[:, :, None] & valid[:, None, :]
+    if seqlen is not None:
+        m = m & (ar[None, None, :] < seqlen.to(device).long()[:, None, None])
+    left, right = (None, None) if window is None else window
+    if causal:
+        right = 0
+    d = ar[None, :] - ar[:, None]  # key - query
+    if left is not None:
+        m = m & (d >= -int(left))[None]
+    if right is not None:
+        m = m & (d <= int(right))[None]
+    return m
 
 
 def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0, causal: bool = False,
-              num_kv_heads: Optional[int] = None):
+              num_kv_heads: Optional[int] = None, segment_ids=None, window=None):
     """Multi-head scaled dot-product attention, token-major inputs: q [B, S, num_heads*64], k and v
     [B, Sk, num_kv_heads*64]. Sk == S is self-attention; Sk != S is cross-attention over a memory of
     another length (a decoder's attention over the encoder's output): the result has the query's
@@ -838,8 +865,21 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
     num_heads % num_kv_heads == 0 and query head h attends key/value head h // (num_heads //
     num_kv_heads) — the heads of a group are contiguous, as torch.repeat_interleave over the head
     axis lays them out. k and v are never repeated in memory, and their gradients come back
-    num_kv_heads*64 wide, each key/value head the sum over the query heads of its group."""
+    num_kv_heads*64 wide, each key/value head the sum over the query heads of its group.
+    Banded masks (self-attention only; they intersect with each other, with causal and with seqlen):
+    segment_ids int32 [B, S] packs several documents into a row — a token attends the tokens of its
+    own maximal run of equal ids (an id that reappears later in the row is another document); a
+    negative id is padding: the token attends nothing and nothing attends it, its output row is
+    exactly zero and so are its gradients. window=(left, right) is sliding-window attention,
+    q - left <= k <= q + right, None on a side for no bound; causal=True clamps right to 0. A row
+    whose intersection is empty behaves like a padding row. GPU: the table of
+    ops.transformer.attention_band and the BAND kernels, which stream only the key tiles of each
+    block's range; CPU: the same mask on the fp32 formulas (zero rows, not NaN). With
+    segment_ids=None and no bound in window the call takes exactly the path it took without them."""
+    from .ops import transformer as T
     B, S, D = q.shape
+    wl, wr = T._band_window(window)
+    banded = segment_ids is not None or wl >= 0 or wr >= 0
     Sk = k.shape[1]
     hd = D // num_heads
     nkv = int(num_heads) if num_kv_heads is None else int(num_kv_heads)
@@ -856,6 +896,13 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
     if causal and Sk != S:
         raise InvalidArgumentError(
             "ttd.nn.attention: causal=True needs as many keys as queries (got %d queries, %d keys)" % (S, Sk))
+    if banded:
+        if Sk != S:
+            raise InvalidArgumentError(
+                "ttd.nn.attention: segment_ids / window are self-attention masks (got %d queries, %d keys)" % (S, Sk))
+        if segment_ids is not None and (tuple(segment_ids.shape) != (B, S) or segment_ids.dtype != torch.int32):
+            raise InvalidArgumentError("ttd.nn.attention: segment_ids must be int32 [batch, seq_len] = [%d, %d], got "
+                                       "%s %s" % (B, S, segment_ids.dtype, tuple(segment_ids.shape)))
     if _on_gpu(q, k, v):
         if hd != 64 or S % 128 != 0 or Sk % 128 != 0 or D % num_heads:
             raise InvalidArgumentError(
@@ -863,6 +910,11 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
                 "(got head_dim %s, seq_len %d%s); pad the sequence (and mask it with seqlen) or use 64-wide heads"
                 % (D / num_heads, S, "" if Sk == S else ", key seq_len %d" % Sk))
         sl = seqlen.to(torch.int32).contiguous() if seqlen is not None else None
+        if banded:
+            ids = segment_ids.to(q.device).contiguous() if segment_ids is not None else None
+            band = T.attention_band(ids, sl.to(q.device) if sl is not None else None, window, causal, B, S,
+                                    out=torch.empty(T.attention_band_ints(B, S), dtype=torch.int32, device=q.device))
+            return _Attention.apply(q, k, v, num_heads, float(dropout_rate), None, int(site), False, nkv, band)
         return _Attention.apply(q, k, v, num_heads, float(dropout_rate), sl, int(site), bool(causal), nkv)
     qh = q.reshape(B, S, num_heads, hd).transpose(1, 2)
     kh = k.reshape(B, Sk, nkv, hd).transpose(1, 2)
@@ -878,7 +930,14 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
     if causal:
         tri = torch.ones((S, S), dtype=torch.bool, device=q.device).tril()
         sc = sc.masked_fill(~tri, float("-inf"))
-    p = sc.softmax(-1)
+    if banded:
+        m = attention_band_mask(segment_ids, seqlen, window, causal, B, S, q.device)
+        sc = sc.masked_fill(~m[:, None], float("-inf"))
+        dead = ~m.any(-1)[:, None, :, None]  # rows that attend nothing: zeros, not softmax's NaN
+        sc = sc.masked_fill(dead, 0.0)
+        p = sc.softmax(-1).masked_fill(dead, 0.0)
+    else:
+        p = sc.softmax(-1)
     if dropout_rate > 0:
         p = F.dropout(p, dropout_rate, training=True)
     return (p @ vh).transpose(1, 2).reshape(B, S, D)

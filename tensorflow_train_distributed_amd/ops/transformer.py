@@ -17,6 +17,9 @@ _lib.register({
     "ttdk_attn_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, I, P],
     "ttdk_attn_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, I, P],
     "ttdk_attn_set_fused_bwd": [I],
+    "ttdk_attn_band": [P, P, I, I, I, I, I, P, P],
+    "ttdk_attn_band_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, P],
+    "ttdk_attn_band_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, P],
     "ttdk_ln_fwd": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
     "ttdk_ln_bwd_num_blocks": [I],
     "ttdk_ln_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, F, I, F, I, P, P],
@@ -69,8 +72,130 @@ class RngState:
 
 
 # ------------------------------------------------------------------ attention
+def _band_window(window):
+    """(left, right) of a window argument as the kernel takes it: -1 for an unbounded side."""
+    if window is None:
+        return -1, -1
+    try:
+        left, right = window
+    except (TypeError, ValueError):
+        raise InvalidArgumentError("attention band: window must be None or (left, right), got %r" % (window,))
+    out = []
+    for side in (left, right):
+        if side is None:
+            out.append(-1)
+            continue
+        if int(side) != side or side < 0:
+            raise InvalidArgumentError(
+                "attention band: a window bound is a non-negative token count or None for no bound, got %r"
+                % (window,))
+        out.append(min(int(side), 1 << 30))
+    return out[0], out[1]
+
+
+def attention_band_ints(B, S):
+    """int32 elements of the band table of B rows of S tokens: a 16-byte record per token and one per
+    128-token block."""
+    return 4 * B * (S + S // 128)
+
+
+def _band_check(segment_ids, seqlen, B, S):
+    if S <= 0 or S % 128:
+        raise InvalidArgumentError("attention band: S must be a positive multiple of 128, got %d" % S)
+    if segment_ids is not None and (tuple(segment_ids.shape) != (B, S) or segment_ids.dtype not in
+                                    (torch.int32, np.dtype("int32"))):
+        raise InvalidArgumentError("attention band: segment_ids must be int32 [B, S] = [%d, %d], got %s %s"
+                                   % (B, S, segment_ids.dtype, tuple(segment_ids.shape)))
+    if seqlen is not None and (tuple(seqlen.shape) != (B,) or seqlen.dtype not in (torch.int32, np.dtype("int32"))):
+        raise InvalidArgumentError("attention band: seqlen must be int32 [B] = [%d], got %s %s"
+                                   % (B, seqlen.dtype, tuple(seqlen.shape)))
+
+
+def attention_band(segment_ids, seqlen, window, causal, B, S, out=None):
+    """The band table of the BAND attention kernels (attention.hip, ttdk_attn_band), built on the
+    device on the current stream: int32 [attention_band_ints(B, S)], into `out` when given (no
+    allocation: a captured step builds it into a per-shape buffer).
+
+    Every query row attends one contiguous key range, the intersection of
+      segment_ids  int32 [B, S] or None: a token attends the tokens of its own maximal run of equal
+                   ids (an id that reappears later in the row is another document); a negative id
+                   is padding — the token attends nothing and nothing attends it: its output row
+                   and its dq / dk / dv rows are exactly zero and its lse is -inf;
+      window       (left, right) or None: q - left <= k <= q + right, None on a side = no bound;
+      causal       clamps right to 0;
+      seqlen       int32 [B] or None: keys >= seqlen[b] are masked, queries never.
+    A row whose intersection is empty behaves like a padding row. Self-attention only.
+    Layout (attention_band_host is the numpy mirror): per token (klo, khi, qlo, qhi) — the keys
+    [klo, khi) query s attends and the queries [qlo, qhi) that attend key s, (S, 0) when empty —
+    then per 128-token block (kt0, kt1, qt0, qt1): the 64-key tiles a query block streams and the
+    64-query tiles a key block streams, qt0 and qt1 even; all zero when the block has nothing."""
+    _band_check(segment_ids, seqlen, B, S)
+    left, right = _band_window(window)
+    dev = segment_ids.device if segment_ids is not None else (seqlen.device if seqlen is not None else None)
+    n = attention_band_ints(B, S)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev if dev is not None else "cuda")
+    elif out.dtype != torch.int32 or out.numel() < n or not out.is_contiguous():
+        raise InvalidArgumentError("attention band: out must be a contiguous int32 tensor of >= %d elements" % n)
+    if segment_ids is not None and not segment_ids.is_contiguous():
+        segment_ids = segment_ids.contiguous()
+    _lib.call("ttdk_attn_band", _p(segment_ids), _p(seqlen), B, S, left, right, int(bool(causal)), out.data_ptr(),
+              _s())
+    return out
+
+
+def attention_band_host(segment_ids, seqlen, window, causal, B, S) -> np.ndarray:
+    """numpy mirror of attention_band: the same int32 table (see there for semantics and layout)."""
+    ids = None if segment_ids is None else np.asarray(segment_ids)
+    sl = None if seqlen is None else np.asarray(seqlen)
+    _band_check(ids, sl, B, S)
+    left, right = _band_window(window)
+    if causal:
+        right = 0
+    tok = np.zeros((B, S, 4), dtype=np.int64)
+    s = np.arange(S)
+    for b in range(B):
+        starts = s == 0
+        if ids is not None:
+            starts[1:] = ids[b, 1:] != ids[b, :-1]
+        rs = np.maximum.accumulate(np.where(starts, s, 0))
+        nxt = np.where(starts, s, S)  # the next run's first token, strictly after s
+        re = np.append(np.minimum.accumulate(nxt[::-1])[::-1][1:], S)
+        n = S if sl is None else min(max(int(sl[b]), 0), S)
+        pad = np.zeros(S, dtype=bool) if ids is None else ids[b] < 0
+        klo, khi, qlo, qhi = rs.copy(), np.minimum(re, n), rs.copy(), re.copy()
+        if left >= 0:
+            klo, qhi = np.maximum(klo, s - left), np.minimum(qhi, s + left + 1)
+        if right >= 0:
+            khi, qlo = np.minimum(khi, s + right + 1), np.maximum(qlo, s - right)
+        ek = pad | (klo >= khi)
+        eq = pad | (s >= n) | (qlo >= qhi)
+        tok[b, :, 0], tok[b, :, 1] = np.where(ek, S, klo), np.where(ek, 0, khi)
+        tok[b, :, 2], tok[b, :, 3] = np.where(eq, S, qlo), np.where(eq, 0, qhi)
+    t = tok.reshape(B, S // 128, 128, 4)
+    lo_k, hi_k, lo_q, hi_q = t[..., 0].min(-1), t[..., 1].max(-1), t[..., 2].min(-1), t[..., 3].max(-1)
+    blk = np.zeros((B, S // 128, 4), dtype=np.int64)
+    blk[..., 0] = np.where(hi_k > 0, lo_k // 64, 0)
+    blk[..., 1] = (hi_k + 63) // 64
+    blk[..., 2] = np.where(hi_q > 0, (lo_q // 64) & ~1, 0)
+    blk[..., 3] = (hi_q + 127) // 128 * 2
+    return np.concatenate([tok.reshape(-1), blk.reshape(-1)]).astype(np.int32)
+
+
+def _band_arg(band, B, S, Sk, causal, seqlen):
+    if Sk is not None and int(Sk) != S:
+        raise InvalidArgumentError(
+            "attention band: the band kernels are self-attention kernels (got %d queries, %d keys)" % (S, Sk))
+    if band.dtype != torch.int32 or band.numel() < attention_band_ints(B, S) or not band.is_contiguous():
+        raise InvalidArgumentError("attention band: band must be the int32 table of attention_band(..., B=%d, S=%d)"
+                                   % (B, S))
+    if causal or seqlen is not None:
+        raise InvalidArgumentError("attention band: causal and seqlen are folded into the table by attention_band; "
+                                   "pass them there, not beside band=")
+
+
 def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, p_drop=0.0, rng=None, site=0,
-                  causal=False):
+                  causal=False, band=None):
     """q/out: 2-D bf16 views [B*S, >= H*64], k/v: [B*Sk, >= Hk*64] (row stride = .stride(0), each its
     own); lse fp32 [B*H, S]. Sk (None: S) is the key length — cross-attention over a memory of
     another length; seqlen then holds the memory's valid lengths (keys >= seqlen[b] masked).
@@ -78,7 +203,18 @@ def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, 
     are not streamed. causal needs Sk == S.
     Hk (None: H) is the number of key/value heads — grouped-query attention (Hk == 1: multi-query):
     H % Hk == 0 and query head h reads key/value head h // (H // Hk), the layout of
-    repeat_interleave over the head axis."""
+    repeat_interleave over the head axis.
+    band (a table of attention_band) runs the BAND kernels: each query row attends the key range the
+    table gives it (documents, windows, causal and seqlen, all folded into the table — so seqlen
+    and causal are not passed beside it), and key tiles outside a block's range are not streamed.
+    Self-attention only: a band with Sk != S raises."""
+    if band is not None:
+        _band_arg(band, B, S, Sk, causal, seqlen)
+        _lib.call("ttdk_attn_band_fwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), band.data_ptr(), B, H,
+                  int(H if Hk is None else Hk), S, S, float(p_drop), _p(rng.t if rng is not None else None),
+                  int(site), _s())
+        return out, lse
     _lib.call("ttdk_attn_fwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
               out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, int(H if Hk is None else Hk), S,
               int(S if Sk is None else Sk), float(p_drop), _p(rng.t if rng is not None else None), int(site),
@@ -96,14 +232,23 @@ def set_fused_attention_bwd(on: bool):
 
 
 def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=None, delta=None, seqlen=None,
-                  p_drop=0.0, rng=None, site=0, causal=False):
-    """Backward of attention_fwd with the same Sk / Hk / seqlen / p_drop / rng / site / causal. dq has
-    the query's B*S rows, dk / dv the keys' B*Sk; delta fp32 [B*H, S]. Sk != S always runs the split
-    kernels (the fused backward is a self-attention kernel), and so does Hk != H: dk / dv then have
-    Hk*64 columns, each key/value head the sum over its H // Hk query heads — summed in fp32
-    registers in head order (deterministic), rounded to bf16 once."""
+                  p_drop=0.0, rng=None, site=0, causal=False, band=None):
+    """Backward of attention_fwd with the same Sk / Hk / seqlen / p_drop / rng / site / causal / band.
+    dq has the query's B*S rows, dk / dv the keys' B*Sk; delta fp32 [B*H, S]. Sk != S always runs the
+    split kernels (the fused backward is a self-attention kernel), and so does Hk != H: dk / dv then
+    have Hk*64 columns, each key/value head the sum over its H // Hk query heads — summed in fp32
+    registers in head order (deterministic), rounded to bf16 once. A band backward always runs the
+    split kernels too (the fused backward has no band form)."""
     if delta is None:
         delta = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
+    if band is not None:
+        _band_arg(band, B, S, Sk, causal, seqlen)
+        _lib.call("ttdk_attn_band_bwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                  v.stride(0), o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(),
+                  delta.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(),
+                  dv.stride(0), band.data_ptr(), B, H, int(H if Hk is None else Hk), S, S, float(p_drop),
+                  _p(rng.t if rng is not None else None), int(site), _s())
+        return dq, dk, dv
     _lib.call("ttdk_attn_bwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
               o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(), delta.data_ptr(),
               dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), _p(seqlen),
