@@ -31,6 +31,8 @@ enum : int {
   kBc2 = 5,     // 1 - beta2^t
   kMaxNorm = 6, // global-norm clip (<= 0: off)
   kGradScale = 7,
+  kOmBeta1 = 8,  // 1 - beta1 and 1 - beta2, rounded once from double: 1.f - hyper[kBeta2] is off
+  kOmBeta2 = 9,  // by 1.3e-5 of its value at beta2 = 0.999 (the rounding of beta2 itself)
 };
 
 __device__ __forceinline__ float clip_factor(const float* hyper, const float* sumsq) {
@@ -98,6 +100,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
                                                    const float* __restrict__ sumsq, int decoupled) {
   const Chunk ch = chunks[blockIdx.x];
   const float lr = hyper[kLr], b1 = hyper[kMu], b2 = hyper[kBeta2], eps = hyper[kEps];
+  const float omb1 = hyper[kOmBeta1], omb2 = hyper[kOmBeta2];
   const float bc1 = hyper[kBc1] > 0.f ? hyper[kBc1] : 1.f, bc2 = hyper[kBc2] > 0.f ? hyper[kBc2] : 1.f;
   const float step = lr * sqrtf(bc2) / bc1;  // TF AdamOptimizer: lr_t = lr*sqrt(1-b2^t)/(1-b1^t)
   const float gs = clip_factor(hyper, sumsq);
@@ -107,8 +110,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
     float wv = w[o];
     float gv = g[o] * gs;
     if (!decoupled) gv += wd * wv;
-    const float mv = b1 * m[o] + (1.f - b1) * gv;
-    const float vv = b2 * v[o] + (1.f - b2) * gv * gv;
+    const float mv = b1 * m[o] + omb1 * gv;
+    const float vv = b2 * v[o] + omb2 * gv * gv;
     m[o] = mv;
     v[o] = vv;
     wv -= step * mv / (sqrtf(vv) + eps);
@@ -132,13 +135,14 @@ __global__ __launch_bounds__(256) void lamb_phase1_kernel(const float* __restric
   __shared__ float red[16];
   const Chunk ch = chunks[blockIdx.x];
   const float b1 = hyper[kMu], b2 = hyper[kBeta2], eps = hyper[kEps];
+  const float omb1 = hyper[kOmBeta1], omb2 = hyper[kOmBeta2];
   const float bc1 = hyper[kBc1] > 0.f ? hyper[kBc1] : 1.f, bc2 = hyper[kBc2] > 0.f ? hyper[kBc2] : 1.f;
   const float gs = clip_factor(hyper, sumsq);
   const float wd = seg_wd ? seg_wd[ch.seg] : 0.f;
   float sw = 0.f, su = 0.f;
   auto one = [&](float wv, float gv, float& mo, float& vo) {
-    const float mv = b1 * mo + (1.f - b1) * gv;
-    const float vv = b2 * vo + (1.f - b2) * gv * gv;
+    const float mv = b1 * mo + omb1 * gv;
+    const float vv = b2 * vo + omb2 * gv * gv;
     mo = mv;
     vo = vv;
     const float uu = (mv / bc1) / (sqrtf(vv / bc2) + eps) + wd * wv;
@@ -267,6 +271,28 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
   if (threadIdx.x == 0) *out = s;
 }
 
+// Sum of squares over the chunk table (the global gradient norm of the clip): partial[chunk] per
+// block, folded by sum_partials_kernel in a fixed order. Only the elements the optimizers
+// update count: alignment padding and the slots of non-trainable variables have no chunk.
+__global__ __launch_bounds__(256) void sumsq_chunks_kernel(const float* __restrict__ x,
+                                                           const Chunk* __restrict__ chunks,
+                                                           float* __restrict__ partial) {
+  __shared__ float red[16];
+  const Chunk ch = chunks[blockIdx.x];
+  float s = 0.f;
+  for (int i = threadIdx.x * 4; i < ch.len; i += blockDim.x * 4) {
+    const long long o = ch.start + i;
+    if (i + 3 < ch.len) {
+      const f32x4_t v = *reinterpret_cast<const f32x4_t*>(x + o);
+      s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    } else {
+      for (int j = i; j < ch.len; ++j) s += x[ch.start + j] * x[ch.start + j];
+    }
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
 // In-graph learning-rate schedule + step counter.
 //   kind 0: constant; 1: exponential decay (staircase flag); 2: polynomial decay with linear warmup;
 //   3: piecewise-linear warmup then cosine.
@@ -348,6 +374,18 @@ TTDK_EXPORT int ttdk_sumsq(const float* x, long long n, float* out, float* parti
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(sumsq_kernel, dim3(static_cast<int>(blocks)), dim3(256), 0, st, x, n, partial);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, partial, static_cast<int>(blocks), out);
+  return hipGetLastError();
+}
+
+// out (fp32 scalar) = sum x^2 over the elements the chunk table covers; `partial`: scratch of
+// >= n_chunks floats.
+TTDK_EXPORT int ttdk_sumsq_chunks(const float* x, const void* chunks, int n_chunks, float* out, float* partial,
+                                  hipStream_t st) {
+  if (!partial || n_chunks < 0) return hipErrorInvalidValue;
+  if (n_chunks > 0)
+    hipLaunchKernelGGL(sumsq_chunks_kernel, dim3(n_chunks), dim3(256), 0, st, x, static_cast<const Chunk*>(chunks),
+                       partial);
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, partial, n_chunks, out);
   return hipGetLastError();
 }
 

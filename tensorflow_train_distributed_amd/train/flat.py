@@ -27,9 +27,9 @@ import torch
 ALIGN = 64  # elements (256 B of fp32): every variable starts 16-B aligned for vector loads
 CHUNK = 16384
 
-HYPER_SIZE = 8
+HYPER_SIZE = 10
 # hyper slots (must match optim.hip)
-H_LR, H_MU, H_BETA2, H_EPS, H_BC1, H_BC2, H_MAXNORM, H_GRADSCALE = range(8)
+H_LR, H_MU, H_BETA2, H_EPS, H_BC1, H_BC2, H_MAXNORM, H_GRADSCALE, H_OMBETA1, H_OMBETA2 = range(10)
 
 
 @dataclass
@@ -229,6 +229,8 @@ class FlatOptimizer:
         self.sched_t = torch.tensor(schedule.params(), dtype=torch.float32, device=dev)
         self.hyper[H_MU] = self.beta1
         self.hyper[H_BETA2] = self.beta2
+        self.hyper[H_OMBETA1] = 1.0 - self.beta1  # rounded once from double (not 1 - fp32(beta))
+        self.hyper[H_OMBETA2] = 1.0 - self.beta2
         self.hyper[H_EPS] = self.eps
         self.hyper[H_MAXNORM] = self.max_grad_norm
         self.hyper[H_GRADSCALE] = 1.0
@@ -263,8 +265,13 @@ class FlatOptimizer:
             _lib.call("ttdk_lr_schedule", self.step_t.data_ptr(), self.sched_t.data_ptr(), self.schedule.kind,
                       self.hyper.data_ptr(), self.beta1, self.beta2, int(increment), _lib.stream())
             if self.max_grad_norm > 0:
-                from ..ops import kernels as K
-                K.sumsq(self.p.grad, out=self._sumsq)
+                # the clip norm is taken over the chunk table: trainable elements only, as
+                # valid_mask() defines it (no alignment padding, no non-trainable slots)
+                chunks, n, _ = self.p.chunk_table()
+                if getattr(self, "_clip_partial", None) is None or self._clip_partial.numel() < n:
+                    self._clip_partial = torch.empty(max(1, n), dtype=torch.float32, device=self.p.device)
+                _lib.call("ttdk_sumsq_chunks", self.p.grad.data_ptr(), chunks.data_ptr(), n, self._sumsq.data_ptr(),
+                          self._clip_partial.data_ptr(), _lib.stream())
         else:
             s = self._host_step
             self.hyper[H_LR] = self.schedule.value(s)
@@ -281,7 +288,9 @@ class FlatOptimizer:
     def _clip_scale_cpu(self):
         gs = float(self.hyper[H_GRADSCALE])
         if self.max_grad_norm > 0:
-            n = float(self._masked_grad().norm()) * gs
+            # accumulated in fp64: torch's fp32 CPU reduction is off by 1e-4 over a few million
+            # elements, ten times the bar on the optimizer state
+            n = float(self._masked_grad().double().norm()) * gs
             if n > self.max_grad_norm:
                 gs *= self.max_grad_norm / n
         return gs
