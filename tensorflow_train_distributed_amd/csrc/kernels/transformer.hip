@@ -64,7 +64,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 8; ++j) sum += f[v][j];
   }
-  const float mean = wave_sum(sum) * (1.f / H);
+  // a true division: sum * (1.f / H) is inexact at H = 1536 (and may be contracted, unrounded,
+  // into s - mean below), which gave a constant row c a deviation of c * 2^-25 instead of 0 for
+  // 1 / sqrt(eps) to multiply. At the power-of-two widths this is the same multiply as before.
+  const float mean = wave_sum(sum) / H;
   float var = 0.f;
 #pragma unroll
   for (int v = 0; v < NV; ++v)
@@ -381,8 +384,12 @@ __global__ __launch_bounds__(256) void embed_bwd_word_kernel(const bf16_t* __res
   }
 }
 
-// dpos[p] (+)= sum_b ds[b*S + p]; dtype[t] (+)= sum over rows with tt == t (T <= 4), via
-// per-thread register sums over a row slice and one atomic per (type, column, block).
+// dpos[p] (+)= sum_b ds[b*S + p], one thread per (position, 8-column chunk).
+// dtype[t] = sum over rows with tt == t (T <= 4; the caller zeroes dtype first): a block owns
+// rows_per_block consecutive rows and splits its 256 threads into 256 / chunks whole groups of
+// chunks = H / 8 threads (H / 8 <= 256), group k walking rows k, k + groups, ... with one
+// thread per 8-column chunk; the 256 % chunks threads left over stay idle. Per-thread register
+// sums, then one atomic per (type, column, thread).
 __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const bf16_t* __restrict__ ds, float* __restrict__ dpos,
                                                             int B, int S, int H, int beta) {
   const long long gid = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;  // (p, chunk)
@@ -407,6 +414,9 @@ __global__ __launch_bounds__(256) void embed_bwd_type_kernel(const bf16_t* __res
   const int chunks = H / 8;
   const int c = (threadIdx.x % chunks) * 8;  // requires H / 8 <= 256 chunks handled per pass
   const int rsub = threadIdx.x / chunks, rstep = 256 / chunks;
+  // the threads past the last whole group (H / 8 does not divide 256: H = 768, 1536) own no row;
+  // they would re-add rows that group 0 already walks. No barrier below: they may leave.
+  if (rsub >= rstep) return;
   float acc[4][8];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
