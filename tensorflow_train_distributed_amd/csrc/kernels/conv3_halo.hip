@@ -30,6 +30,25 @@
 //    outputs per wave (7 x 2 MFMA blocks: each A fragment feeds 2 MFMAs, each B fragment 7);
 //  * epilogue shared with the streaming pointwise kernel (stream_epi.h / epi_rows): BN partial
 //    statistics per tile, or the next unit's ReLU-masked gradient + BN-backward sums (dgrad).
+//
+// Schedule (template parameter SCHED; 1 is the default, 0 its predecessor, kept selectable at
+// run time for A/Bs: TTD_CONV3_SCHED / ttdk_set_conv3_sched; outputs are bit-identical, the
+// accumulation order of every output element is the same):
+//  * nothing derived from the thread index alone is held across the tile loop: a staging pass
+//    recomputes its per-slot halo coordinates from an opaque copy of the index (fresh()). Held,
+//    they were hoisted out of the persistent loop and spilled;
+//  * each k-step issues its 9 fragment reads as one pinned burst in the order the MFMAs consume
+//    them (frag_fence()), so counted lgkmcnt waits overlap the later reads with the earlier
+//    MFMAs. Unpinned, the compiler interleaved read, lgkmcnt(0), two MFMAs;
+//  * per tile: stage (prologue, side stores), barrier, next tile's halo loads, 9 taps x 2 k-steps
+//    of MFMAs, barrier, accumulators to LDS over the halo, barrier, epilogue rows, statistics,
+//    barrier. Staging and epilogue are still exposed: no wave computes while another stores.
+//
+// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage), SCHED 1 / SCHED 0:
+//   conv3_kernel<64,64,8,56,PRO 0,fwd|flip,4>  219 VGPR, scratch 0   / 251 VGPR, scratch 0
+//   conv3_kernel<64,64,8,56,PRO 1,fwd,4>       226 VGPR, scratch 0   / 256 VGPR, scratch 80 B
+//   conv3_kernel<64,64,4,56,PRO 2,flip,2>      237 VGPR, scratch 0   / 256 VGPR, scratch 56 B
+//   0 AGPRs, 2 waves/SIMD; LDS 149,504 B (PRO 2: 118,784 B).
 #include "stream_epi.h"
 
 namespace ttdk {
@@ -65,7 +84,30 @@ __device__ __forceinline__ int slot_chunk(int q) { return (q >> 3) % CP; }
 template <int CP>
 __device__ __forceinline__ int slot_pix(int q) { return (q & 7) + 8 * (q / (8 * CP)); }
 
-template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM>
+// SCHED 1: hand the compiler an opaque copy of the (loop-invariant) thread index. What is derived
+// from it (the per-slot halo coordinates and offsets of a staging pass) is then recomputed at
+// every use, a few VALU per slot, instead of being hoisted out of the persistent tile loop and
+// held, or spilled, across the MFMA loop.
+template <int SCHED>
+__device__ __forceinline__ int fresh(int tid) {
+  if constexpr (SCHED != 0) {
+    asm volatile("" : "+v"(tid));
+    __builtin_assume(tid >= 0 && tid < THR);
+  }
+  return tid;
+}
+
+// SCHED 1: pin a k-step's fragment reads as one burst in program order (one fence after each),
+// apart from its MFMAs. Left alone the compiler saves registers by re-ordering every step into
+// read, lgkmcnt(0), two MFMAs, seven times over, which exposes the LDS latency to every MFMA
+// pair; with the burst first and in the order the MFMAs consume it, its own counted lgkmcnt
+// waits let the later reads land under the earlier MFMAs.
+template <int SCHED>
+__device__ __forceinline__ void frag_fence() {
+  if constexpr (SCHED != 0) __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM, int SCHED>
 __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __restrict__ w, EpiParams E, int H,
                                                       int N, int tiles, int nslices) {
   constexpr int BM = TH * W;              // output pixels per tile
@@ -132,11 +174,12 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
   uint32_t rm[(NA + 3) / 4];  // PRO 2: ReLU mask bytes, four per register
   auto load_tile = [&](int t) {
     const int img = t / tiles_per_img, h0 = (t % tiles_per_img) * TH;
+    const int ft = fresh<SCHED>(tid);
 #pragma unroll
     for (int i = 0; i < (NA + 3) / 4; ++i) rm[i] = 0;
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      const int pix = slot_pix<CP>(tid + THR * i);
+      const int pix = slot_pix<CP>(ft + THR * i);
       const int hr = pix / HC, hc = pix % HC;
       const int h = h0 - 1 + hr, x = hc - 1;
       const bool ok = pix < NPIX && h >= 0 && h < H && x >= 0 && x < W;
@@ -159,10 +202,11 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
       load8f(pa.s + C + ac * 8, k1);
       load8f(pa.s + 2 * C + ac * 8, k2);
     }
+    const int ft = fresh<SCHED>(tid);
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      const int pix = slot_pix<CP>(tid + THR * i);
-      if (tid + THR * i >= NCH) break;
+      const int pix = slot_pix<CP>(ft + THR * i);
+      if (ft + THR * i >= NCH) break;
       const int hr = pix / HC, hc = pix % HC;
       const int h = h0 - 1 + hr, x = hc - 1;
       const bool ok = h >= 0 && h < H && x >= 0 && x < W;
@@ -225,13 +269,20 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
         const int kchunk = ((kglob & 63) >> 3) + (lane >> 4);
         bf16x8_t af[TM], bfr[TN];
 #pragma unroll
-        for (int c = 0; c < TN; ++c) bfr[c] = lds_read_b128(pB + kmaj_off(wn * WC + c * 16 + (lane & 15), kchunk));
+        for (int c = 0; c < TN; ++c) {
+          bfr[c] = lds_read_b128(pB + kmaj_off(wn * WC + c * 16 + (lane & 15), kchunk));
+          frag_fence<SCHED>();
+        }
 #pragma unroll
-        for (int a = 0; a < TM; ++a) af[a] = lds_read_b128(abase[a] + kc * 4 * REG + tq * 16);
+        for (int a = 0; a < TM; ++a) {
+          af[a] = lds_read_b128(abase[a] + kc * 4 * REG + tq * 16);
+          frag_fence<SCHED>();
+        }
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
           for (int c = 0; c < TN; ++c) acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c], af[a], acc[a][c], 0, 0, 0);
+        frag_fence<SCHED>();
       }
     }
     __syncthreads();  // every wave is done reading the halo: stage the tile over it
@@ -263,7 +314,7 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
   }
 }
 
-template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM>
+template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM, int SCHED>
 hipError_t launch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, int H, int N, hipStream_t st) {
   const int nsl = N / BN;
   const int tiles = Nimg * (H / TH);
@@ -271,8 +322,8 @@ hipError_t launch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, 
   if (per_xcd < 1) per_xcd = 1;
   const int need = ceil_div(tiles, 8);
   if (per_xcd > need) per_xcd = need;
-  hipLaunchKernelGGL((conv3_kernel<C, BN, TH, W, PRO, FLIP, WM>), dim3(8 * nsl * per_xcd), dim3(THR), 0, st, pa, w, E, H, N,
-                     tiles, nsl);
+  hipLaunchKernelGGL((conv3_kernel<C, BN, TH, W, PRO, FLIP, WM, SCHED>), dim3(8 * nsl * per_xcd), dim3(THR), 0, st, pa, w,
+                     E, H, N, tiles, nsl);
   return hipGetLastError();
 }
 
@@ -284,12 +335,12 @@ inline int pick_th(int C, int N, int W, int pro) {
   return 0;
 }
 
-template <int PRO, bool FLIP>
+template <int PRO, bool FLIP, int SCHED>
 hipError_t dispatch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, int H, int W, int C, int N,
                     hipStream_t st) {
   if (C == 64 && N == 64 && W == 56) {
-    if constexpr (PRO == 2) return launch<64, 64, 4, 56, PRO, FLIP, 2>(pa, w, E, Nimg, H, N, st);
-    else return launch<64, 64, 8, 56, PRO, FLIP, 4>(pa, w, E, Nimg, H, N, st);
+    if constexpr (PRO == 2) return launch<64, 64, 4, 56, PRO, FLIP, 2, SCHED>(pa, w, E, Nimg, H, N, st);
+    else return launch<64, 64, 8, 56, PRO, FLIP, 4, SCHED>(pa, w, E, Nimg, H, N, st);
   }
   return hipErrorInvalidValue;
 }
@@ -308,7 +359,26 @@ hipError_t dispatch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg
 // producing BN + ReLU on the way and writes the interior back once), and streams the filter one
 // tap (128 x 128 bf16 = 32 KiB) at a time through two LDS buffers by LDS-DMA: tap t + 1 lands
 // under tap t's 56 MFMAs per wave. L2 traffic per output row: ~1.7 KB (halo once, filter once
-// per 224 rows). The next tile's halo is prefetched into registers under this tile's epilogue.
+// per 224 rows).
+//
+// Schedule (SCHED as above; per tile: stage, barrier, 9 taps each ending in a wait and a
+// barrier, accumulators to LDS over the halo, barrier, epilogue rows, statistics, barrier):
+//  * SCHED 1: the tap loop is unrolled and the next tile's halo is prefetched into registers
+//    UNDER it, two of its 12 loads per tap in taps 0-5, each pair issued after that tap's filter
+//    DMA. VMEM retires in issue order, so the wait ending tap k is vmcnt(2): it covers tap
+//    k + 1's filter, the halo loads of tap k - 1 and all older stores (the side stores of the
+//    staging drain under tap 0, not before it) and leaves tap k's own two loads in flight. The
+//    wait is vmcnt(0) when no tile follows, and in taps 6-8, which ends the tile with the next
+//    tile's tap 0 and its whole halo landed;
+//  * SCHED 1 also holds one source address per DMA piece across the tile loop and adds the tap's
+//    offset at issue; the 36 (piece, tap) addresses, and the staging coordinates, were what the
+//    predecessor precomputed ahead of the loop and spilled. Fragment reads are pinned as above;
+//  * SCHED 0: `#pragma unroll 1` tap loop, vmcnt(0) at every tap and before tap 0, the next
+//    tile's halo issued after the tap loop (it flies under the epilogue only).
+//
+// Resources (as above), SCHED 1 / SCHED 0, LDS 159,744 B, 0 AGPRs, 2 waves/SIMD:
+//   conv3s_kernel<128,128,8,28,28,PRO 0,fwd|flip>  239 VGPR, scratch 0  / 256 VGPR, scratch 144 B
+//   conv3s_kernel<128,128,8,28,28,PRO 1,fwd>       245 VGPR, scratch 0  / 256 VGPR, scratch 276 B
 namespace c3s {
 
 constexpr int THR = 512;
@@ -332,8 +402,17 @@ template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// at most n (0 .. 3; a constant once the tap loop is unrolled) VMEM operations left in flight
+__device__ __forceinline__ void wait_vm_upto(int n) {
+  switch (n) {
+    case 1: wait_vm<1>(); break;
+    case 2: wait_vm<2>(); break;
+    case 3: wait_vm<3>(); break;
+    default: wait_vm<0>(); break;
+  }
+}
 
-template <int C, int BN, int TR, int H, int W, int PRO, bool FLIP>
+template <int C, int BN, int TR, int H, int W, int PRO, bool FLIP, int SCHED>
 __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t* __restrict__ w, EpiParams E,
                                                        int rows_total, int N, int tiles) {
   constexpr int WM = 2, WN = NW / WM;
@@ -370,6 +449,15 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
   const bool write_side = pa.side != nullptr;
   const int nimg = rows_total / H;
 
+  // SCHED 1: the lane's tap-0 source of each DMA piece, held across the tile loop
+  const bf16_t* wsrc[NDMA];
+#pragma unroll
+  for (int i = 0; i < NDMA; ++i) {
+    const int L = (i * NW + wave) * 64 + lane;
+    const int sub = L / (BN * 8), p = L % (BN * 8), row = p >> 3, j = p & 7;
+    const int sc = j ^ ((row >> 1) & 7);
+    wsrc[i] = w + static_cast<long long>(row) * 9 * C + (sub * 8 + sc) * 8;
+  }
   // one filter tap into buffer `buf` (K-major [BN][C], kmaj_off layout in 64-k sub-tiles: linear
   // LDS chunk L holds logical chunk (L % 8) ^ swz(row) of its row)
   auto dma_tap = [&](int tap, int buf) {
@@ -377,11 +465,19 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
     char* dst = sBb + buf * SBT;
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) {
-      const int L = (i * NW + wave) * 64 + lane;
-      const int sub = L / (BN * 8), p = L % (BN * 8), row = p >> 3, j = p & 7;
-      const int sc = j ^ ((row >> 1) & 7);
-      dma16(w + (static_cast<long long>(row) * 9 + stap) * C + (sub * 8 + sc) * 8,
-            lds_addr(dst + (i * NW + wave) * 1024));
+      if constexpr (SCHED != 0) {
+        // an opaque tap offset: src = wsrc[i] + off is formed here (two VALU), not once per
+        // (piece, tap) ahead of the tile loop, where the 36 addresses spilled
+        int off = stap * C;
+        asm volatile("" : "+s"(off));
+        dma16(wsrc[i] + off, lds_addr(dst + (i * NW + wave) * 1024));
+      } else {
+        const int L = (i * NW + wave) * 64 + lane;
+        const int sub = L / (BN * 8), p = L % (BN * 8), row = p >> 3, j = p & 7;
+        const int sc = j ^ ((row >> 1) & 7);
+        dma16(w + (static_cast<long long>(row) * 9 + stap) * C + (sub * 8 + sc) * 8,
+              lds_addr(dst + (i * NW + wave) * 1024));
+      }
     }
   };
   // tile geometry: rows [R0, R0 + n0) of image i0 (from local row h0), then n1 rows of i0 + 1
@@ -413,20 +509,23 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
   };
 
   uint4 ra[NA];
+  // halo slot tid + THR * i of tile geometry q into ra[i]
+  auto load_slot = [&](const Geo& q, int ft, int i) {
+    const int qq = ft + THR * i;
+    const int pix = c3::slot_pix<CP>(qq);
+    const int s = pix / HC, x = pix % HC - 1;
+    int img, h;
+    bool interior;
+    const bool ok = qq < NCH && slot_src(q, s, img, h, interior) && h >= 0 && h < H && x >= 0 && x < W;
+    const long long off = ((static_cast<long long>(img) * H + h) * W + x) * C + ac * 8;
+    // always one load per slot (the zero page otherwise): the counted waits below rely on it
+    ra[i] = ldg16(ok ? pa.x + off : reinterpret_cast<const bf16_t*>(big::g_zero));
+  };
   auto load_tile = [&](int t) {
     const Geo q = geo(t);
+    const int ft = c3::fresh<SCHED>(tid);
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int qq = tid + THR * i;
-      const int pix = c3::slot_pix<CP>(qq);
-      const int s = pix / HC, x = pix % HC - 1;
-      int img, h;
-      bool interior;
-      const bool ok = qq < NCH && slot_src(q, s, img, h, interior) && h >= 0 && h < H && x >= 0 && x < W;
-      const long long off = ((static_cast<long long>(img) * H + h) * W + x) * C + ac * 8;
-      // always one load per slot (the zero page otherwise): the counted waits below rely on it
-      ra[i] = ldg16(ok ? pa.x + off : reinterpret_cast<const bf16_t*>(big::g_zero));
-    }
+    for (int i = 0; i < NA; ++i) load_slot(q, ft, i);
   };
   auto stage_tile = [&](int t) {
     const Geo q = geo(t);
@@ -435,9 +534,10 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
       c3::load8f(pa.s + ac * 8, k0);
       c3::load8f(pa.b + ac * 8, k1);
     }
+    const int ft = c3::fresh<SCHED>(tid);
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      const int qq = tid + THR * i;
+      const int qq = ft + THR * i;
       if (qq >= NCH) break;
       const int pix = c3::slot_pix<CP>(qq);
       const int s = pix / HC, x = pix % HC - 1;
@@ -475,6 +575,7 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
   if (t < tiles) {
     dma_tap(0, 0);
     load_tile(t);
+    if constexpr (SCHED != 0) wait_vm<0>();  // the first tile's tap 0 (stage_tile waits for the halo anyway)
   }
   for (; t < tiles; t += G) {
     const Geo q = geo(t);
@@ -486,7 +587,10 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
       abase[a] = (lane >> 4) * REG + ((j + (j >= q.n0 ? 2 : 0)) * HC + col) * 16;
     }
     stage_tile(t);
-    wait_vm<0>();  // this tile's tap 0 (and every earlier store) landed
+    // SCHED 0: this tile's tap 0 (and every earlier store) landed. SCHED 1: tap 0 was retired at
+    // the previous tile's last tap (before the loop for the first tile); the side stores just
+    // issued drain under tap 0
+    if constexpr (SCHED == 0) wait_vm<0>();
     __syncthreads();
     const bool more = t + G < tiles;
     f32x4_t acc[TM][TN];
@@ -494,11 +598,28 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
     for (int a = 0; a < TM; ++a)
 #pragma unroll
       for (int c = 0; c < TN; ++c) acc[a][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
+    // SCHED 1: the next tile's halo flies under this tile's MFMAs. The tap loop is unrolled, and
+    // taps 0 .. NA / HPT - 1 issue HPT of its NA loads each, AFTER their filter DMA. VMEM retires
+    // in issue order, so the wait that ends tap k, vmcnt(HPT), covers tap k + 1's filter, the halo
+    // loads of tap k - 1 and all older stores, and leaves only tap k's own halo loads in flight
+    // (at least one tap of cover each). Without a next tile nothing is issued after the DMA and
+    // the wait is vmcnt(0).
+    constexpr int HPT = 2;
+    static_assert(HPT * 8 >= NA, "the halo loads are all retired by the wait of the last tap");
+    const Geo qn = geo(SCHED != 0 && more ? t + G : t);
+#pragma unroll(SCHED != 0 ? 9 : 1)
     for (int tap = 0; tap < 9; ++tap) {
       const int bnext = bcur ^ 1;
       if (tap < 8) dma_tap(tap + 1, bnext);
       else if (more) dma_tap(0, bnext);
+      const int h0 = tap * HPT < NA ? tap * HPT : NA, h1 = h0 + HPT < NA ? h0 + HPT : NA;
+      if constexpr (SCHED != 0) {
+        if (more) {
+          const int ft = c3::fresh<SCHED>(tid);
+#pragma unroll
+          for (int i = h0; i < h1; ++i) load_slot(qn, ft, i);
+        }
+      }
       const char* sBc = sBb + bcur * SBT;
       const int tq = ((tap / 3) * HC + (tap % 3)) * 16;
 #pragma unroll
@@ -508,23 +629,32 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
         const int kchunk = ((kglob & 63) >> 3) + (lane >> 4);
         bf16x8_t af[TM], bfr[TN];
 #pragma unroll
-        for (int c = 0; c < TN; ++c) bfr[c] = lds_read_b128(pB + kmaj_off(wn * WC + c * 16 + (lane & 15), kchunk));
+        for (int c = 0; c < TN; ++c) {
+          bfr[c] = lds_read_b128(pB + kmaj_off(wn * WC + c * 16 + (lane & 15), kchunk));
+          c3::frag_fence<SCHED>();
+        }
 #pragma unroll
-        for (int a = 0; a < TM; ++a) af[a] = lds_read_b128(sA + abase[a] + kc * 4 * REG + tq);
+        for (int a = 0; a < TM; ++a) {
+          af[a] = lds_read_b128(sA + abase[a] + kc * 4 * REG + tq);
+          c3::frag_fence<SCHED>();
+        }
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
           for (int c = 0; c < TN; ++c) acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c], af[a], acc[a][c], 0, 0, 0);
+        c3::frag_fence<SCHED>();
       }
-      wait_vm<0>();  // the next tap's DMA landed
+      if constexpr (SCHED != 0) wait_vm_upto(more ? h1 - h0 : 0);  // the next tap's DMA landed (see above)
+      else wait_vm<0>();                                           // the next tap's DMA landed
       __syncthreads();
       bcur = bnext;
     }
     // (the last barrier above: every wave is done reading the halo) stage the tile over it
     sepi::stage_acc<TM, TN, WR, WC, PITCH>(sA, acc, wm, wn, lane, epi_alpha(E));
-    // the next tile's halo into registers now that the accumulators are dead: it flies under this
-    // tile's epilogue (prefetching it across the tap loop held 48 more VGPRs there and spilled)
-    if (more) load_tile(t + G);
+    // SCHED 0: the next tile's halo into registers now that the accumulators are dead: it flies
+    // under this tile's epilogue only
+    if constexpr (SCHED == 0)
+      if (more) load_tile(t + G);
     __syncthreads();
     constexpr int ECPR = BN / 8;
     constexpr int RPP = THR / ECPR;
@@ -552,7 +682,7 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
   }
 }
 
-template <int PRO, bool FLIP>
+template <int PRO, bool FLIP, int SCHED>
 hipError_t launch(const c3::Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, int N, hipStream_t st) {
   const int rows = Nimg * 28;
   const int tiles = ceil_div(rows, 8);
@@ -560,8 +690,8 @@ hipError_t launch(const c3::Pro& pa, const bf16_t* w, const EpiParams& E, int Ni
   if (G < 8) G = 8;
   const int need = ceil_div(tiles, 8) * 8;
   if (G > need) G = need;
-  hipLaunchKernelGGL((conv3s_kernel<128, 128, 8, 28, 28, PRO, FLIP>), dim3(G), dim3(THR), 0, st, pa, w, E, rows, N,
-                     tiles);
+  hipLaunchKernelGGL((conv3s_kernel<128, 128, 8, 28, 28, PRO, FLIP, SCHED>), dim3(G), dim3(THR), 0, st, pa, w, E, rows,
+                     N, tiles);
   return hipGetLastError();
 }
 
@@ -580,7 +710,19 @@ int& conv3_s3_flag() {
   static int on = getenv_int("TTD_CONV3_S3", 1);  // stage-3 streamed-filter variant (0: off)
   return on;
 }
+int& conv3_sched_flag() {
+  static int on = getenv_int("TTD_CONV3_SCHED", 1);  // 1: the schedule described above; 0: its predecessor (A/B)
+  return on;
+}
 }  // namespace
+
+// Runtime switch between the two schedules of both halo kernels (template parameter SCHED);
+// returns the previous setting. Results are bit-identical under both.
+TTDK_EXPORT int ttdk_set_conv3_sched(int on) {
+  const int old = conv3_sched_flag();
+  conv3_sched_flag() = on ? 1 : 0;
+  return old;
+}
 
 // Runtime switch of the stage-3 streamed-filter variant; returns the previous setting.
 TTDK_EXPORT int ttdk_set_conv3_s3(int on) {
@@ -602,6 +744,7 @@ TTDK_EXPORT int ttdk_conv3_rows(int H, int W, int C, int N, int pro) {
 TTDK_EXPORT int ttdk_conv3_halo(const bf16_t* x, const bf16_t* x2, const uint8_t* mask_in, const float* s,
                                 const float* b, bf16_t* side, uint8_t* side_mask, int pro, int flip, const bf16_t* w,
                                 int Nimg, int H, int W, int C, int N, const TtdkEpilogue* epi, hipStream_t st) {
+  const int sched = conv3_sched_flag();
   if (ttdk_conv3_rows(H, W, C, N, pro) == 8 * W && c3s::fits(H, W, C, N, pro)) {
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return hipErrorInvalidValue;
     const EpiParams e = to_epi(epi);
@@ -609,9 +752,13 @@ TTDK_EXPORT int ttdk_conv3_halo(const bf16_t* x, const bf16_t* x2, const uint8_t
     if (pro == 1 && (!s || !b)) return hipErrorInvalidValue;
     if (side_mask && pro != 1) return hipErrorInvalidValue;
     const c3::Pro pa{x, nullptr, nullptr, s, b, side, side_mask};
-    if (pro == 0 && !flip) return c3s::launch<0, false>(pa, w, e, Nimg, N, st);
-    if (pro == 0 && flip) return c3s::launch<0, true>(pa, w, e, Nimg, N, st);
-    if (pro == 1 && !flip) return c3s::launch<1, false>(pa, w, e, Nimg, N, st);
+#define C3S_CASE(P_, F_)              \
+  if (pro == P_ && (flip != 0) == F_) \
+    return sched ? c3s::launch<P_, F_, 1>(pa, w, e, Nimg, N, st) : c3s::launch<P_, F_, 0>(pa, w, e, Nimg, N, st);
+    C3S_CASE(0, false)
+    C3S_CASE(0, true)
+    C3S_CASE(1, false)
+#undef C3S_CASE
     return hipErrorInvalidValue;
   }
   const int th = c3::pick_th(C, N, W, pro);
@@ -622,8 +769,10 @@ TTDK_EXPORT int ttdk_conv3_halo(const bf16_t* x, const bf16_t* x2, const uint8_t
   if (pro == 2 && (!s || !x2)) return hipErrorInvalidValue;
   if (side_mask && pro != 1) return hipErrorInvalidValue;
   const c3::Pro pa{x, x2, mask_in, s, b, side, side_mask};
-#define C3_CASE(P_, F_) \
-  if (pro == P_ && (flip != 0) == F_) return c3::dispatch<P_, F_>(pa, w, e, Nimg, H, W, C, N, st);
+#define C3_CASE(P_, F_)                                                           \
+  if (pro == P_ && (flip != 0) == F_)                                             \
+    return sched ? c3::dispatch<P_, F_, 1>(pa, w, e, Nimg, H, W, C, N, st)        \
+                 : c3::dispatch<P_, F_, 0>(pa, w, e, Nimg, H, W, C, N, st);
   C3_CASE(0, false)
   C3_CASE(1, false)
   C3_CASE(0, true)

@@ -139,7 +139,8 @@ class ResNet:
         self.fuse_c3 = os.environ.get("TTD_FUSE_C3", "1") != "0"
         # halo-kernel data gradient of those convs: 2 = after the BN-backward pass, with the feeding
         # unit's BN-backward sums in its epilogue (tools/conv3_bench.py: 648 -> 529 us at b1024);
-        # 1 = with the BN backward as its operand prologue (slower: 920 vs 863 us incl. the pass)
+        # 1 = with the BN backward as its operand prologue (slower: 920 vs 863 us incl. the pass;
+        # with the kernels' current schedule 787 vs 673 us)
         self.c3_dgrad = int(os.environ.get("TTD_C3_DGRAD", "2"))
         # 1x1 data gradients on the 256-row kernel form the unit's BN backward (dz = a*g + b*y + c)
         # in LDS as their operand and store dz for the weight gradient: no separate backward-apply

@@ -298,6 +298,15 @@ def set_conv3_s3(on: bool) -> bool:
     return bool(_lib.query("ttdk_set_conv3_s3", 1 if on else 0))
 
 
+_lib.register({"ttdk_set_conv3_sched": [_lib.I]})
+
+
+def set_conv3_sched(new: bool) -> bool:
+    """Switch both halo 3x3 kernels between their current schedule and its predecessor
+    (TTD_CONV3_SCHED; an A/B switch: results are bit-identical); returns the previous setting."""
+    return bool(_lib.query("ttdk_set_conv3_sched", 1 if new else 0))
+
+
 def conv3_rows(H, W, C, N, pro=0):
     """Output pixels per tile of the halo 3x3 kernel (conv3_halo.hip) for a [*, H, W, C] -> N
     3x3/s1/p1 conv with prologue `pro` (0 none, 1 BN forward, 2 BN backward), or 0 when the
