@@ -42,12 +42,29 @@
 //    MFMAs. Unpinned, the compiler interleaved read, lgkmcnt(0), two MFMAs;
 //  * per tile: stage (prologue, side stores), barrier, next tile's halo loads, 9 taps x 2 k-steps
 //    of MFMAs, barrier, accumulators to LDS over the halo, barrier, epilogue rows, statistics,
-//    barrier. Staging and epilogue are still exposed: no wave computes while another stores.
+//    barrier. The staging pass is still exposed: no wave computes while another stages;
+//  * the epilogue's thread index goes through fresh() too: its row addresses, held across the
+//    tile loop, cost every SCHED 1 instantiation 12-20 VGPRs.
+//
+// Feeding epilogue (template parameter FEED, SCHED 1 data gradients; TTD_CONV3_FEED /
+// ttdk_set_conv3_feed, 0 = epi_rows as before; bit-identical): a data gradient that feeds the
+// next BN's backward sums (by + bmask set, nothing else in the epilogue) read each of a thread's
+// 7 rows (4 at TH 4) of by / bmask in `unroll 1` batches of two, four dependent HBM round trips
+// per tile behind a 64-bit row multiply and the run-time flags of epi_rows. With FEED 1
+// (stream_epi.h: feed_batch_*) the first three rows (two at TH 4) are loaded at tap 6, under the
+// last MFMAs, the rest right after stage_acc, when the accumulators are dead and before the
+// barrier that publishes the staged tile; the row loop then reads LDS, masks, packs, stores and
+// sums, with counted vmcnt waits, and row addresses advance by a constant. FEED is a template
+// parameter picked on the host: as a run-time branch the conditional loads made the compiler's
+// vmcnt bookkeeping fall back to vmcnt(0) at the first row, and carried both epilogues'
+// registers (253-256 VGPRs).
 //
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage), SCHED 1 / SCHED 0:
-//   conv3_kernel<64,64,8,56,PRO 0,fwd|flip,4>  219 VGPR, scratch 0   / 251 VGPR, scratch 0
-//   conv3_kernel<64,64,8,56,PRO 1,fwd,4>       226 VGPR, scratch 0   / 256 VGPR, scratch 80 B
-//   conv3_kernel<64,64,4,56,PRO 2,flip,2>      237 VGPR, scratch 0   / 256 VGPR, scratch 56 B
+//   conv3_kernel<64,64,8,56,PRO 0,fwd|flip,4>         207 VGPR, scratch 0   / 251 VGPR, scratch 0
+//   conv3_kernel<64,64,8,56,PRO 0,flip,4,FEED 1>      204 VGPR, scratch 0
+//   conv3_kernel<64,64,8,56,PRO 1,fwd,4>              214 VGPR, scratch 0   / 256 VGPR, scratch 80 B
+//   conv3_kernel<64,64,4,56,PRO 2,flip,2>             232 VGPR, scratch 0   / 256 VGPR, scratch 56 B
+//   conv3_kernel<64,64,4,56,PRO 2,flip,2,FEED 1>      166 VGPR, scratch 0
 //   0 AGPRs, 2 waves/SIMD; LDS 149,504 B (PRO 2: 118,784 B).
 #include "stream_epi.h"
 
@@ -107,7 +124,7 @@ __device__ __forceinline__ void frag_fence() {
   if constexpr (SCHED != 0) __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM, int SCHED>
+template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM, int SCHED, int FEED>
 __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __restrict__ w, EpiParams E, int H,
                                                       int N, int tiles, int nslices) {
   constexpr int BM = TH * W;              // output pixels per tile
@@ -248,12 +265,28 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
     }
   };
 
+  // epilogue mapping: a thread owns 16-B column chunk tid % ECPR of rows tid / ECPR + k * RPP
+  constexpr int ECPR = BN / 8;
+  constexpr int RPP = THR / ECPR;
+  constexpr int NR = (BM + RPP - 1) / RPP;
+  // FEED 1 (the host picks it for sepi::feed_case(E) with full slices; data gradients under
+  // SCHED 1): prefetched feeding epilogue (stream_epi.h). Rows [0, FA) of by / bmask are loaded
+  // under the tap loop, at tap FTAP, rows [FA, NR) after stage_acc, when the accumulators are
+  // dead. A template parameter, not a run-time branch: with the loads in conditional blocks the
+  // compiler's vmcnt bookkeeping fell back to vmcnt(0) at the first row
+  constexpr int FA = NR >= 6 ? 3 : 2, FTAP = 6;
+  static_assert(FEED == 0 || (FLIP && SCHED != 0), "feeding epilogue: data gradients under SCHED 1");
+  const int M = tiles * BM;
+
   int t = g;
   if (t < tiles) load_tile(t);
   for (; t < tiles; t += G) {
     stage_tile(t);
     __syncthreads();
     if (t + G < tiles) load_tile(t + G);  // in flight under this tile's MFMAs and epilogue
+    const int m0 = t * BM;
+    sepi::FeedBatch<FA> fa;  // (declared per tile: not carried around the tile loop)
+    sepi::FeedBatch<NR - FA> fb;
     f32x4_t acc[TM][TN];
 #pragma unroll
     for (int a = 0; a < TM; ++a)
@@ -264,6 +297,12 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
       const int tq = (tap / 3) * HC + (tap % 3);
 #pragma unroll
       for (int kc = 0; kc < C / 32; ++kc) {
+        if constexpr (FEED != 0) {
+          if (tap == FTAP && kc == 0) {
+            const int ft = fresh<SCHED>(tid);
+            sepi::feed_batch_load<BM, RPP, FA>(fa, E, 0, ft / ECPR, m0, M, n0 + (ft % ECPR) * 8);
+          }
+        }
         const int kglob = tap * C + kc * 32;  // first k of this 32-wide step
         const char* pB = sB + (kglob >> 6) * (BN * 128);
         const int kchunk = ((kglob & 63) >> 3) + (lane >> 4);
@@ -286,13 +325,12 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
       }
     }
     __syncthreads();  // every wave is done reading the halo: stage the tile over it
-    sepi::stage_acc<TM, TN, WR, WC, PITCH>(sA, acc, wm, wn, lane, epi_alpha(E));
-    __syncthreads();
-    constexpr int ECPR = BN / 8;
-    constexpr int RPP = THR / ECPR;
-    const int m0 = t * BM;
-    const int c = tid % ECPR, r0 = tid / ECPR;
+    const int fe = fresh<SCHED>(tid);  // (the row addresses of the epilogue are not held across the tile loop either)
+    const int c = fe % ECPR, r0 = fe / ECPR;
     const int n = n0 + c * 8;
+    sepi::stage_acc<TM, TN, WR, WC, PITCH>(sA, acc, wm, wn, lane, epi_alpha(E));
+    if constexpr (FEED != 0) sepi::feed_batch_load<BM, RPP, NR - FA>(fb, E, FA, r0, m0, M, n);
+    __syncthreads();
     const bool nfull = n + 8 <= N;
     const bool vst = nfull && (E.ldo & 7) == 0;
     float bias8[8], s8[8], q8[8], r8[8];
@@ -301,8 +339,10 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
       bias8[j] = (E.bias && n + j < N) ? E.bias[n + j] : 0.f;
       s8[j] = q8[j] = r8[j] = 0.f;
     }
-    const int M = tiles * BM;
-    if (E.beta || E.residual || E.by)
+    if constexpr (FEED != 0) {
+      sepi::feed_batch_rows<BM, RPP, PITCH, FA>(fa, E, sA, 0, c, r0, m0, M, n, s8, q8);
+      sepi::feed_batch_rows<BM, RPP, PITCH, NR - FA>(fb, E, sA, FA, c, r0, m0, M, n, s8, q8);
+    } else if (E.beta || E.residual || E.by)
       epi_rows<BM, RPP, PITCH, true, 2>(E, sA, c, r0, n, m0, M, N, vst, vst, bias8, s8, q8, r8);
     else
       epi_rows<BM, RPP, PITCH, false>(E, sA, c, r0, n, m0, M, N, vst, vst, bias8, s8, q8, r8);
@@ -314,7 +354,7 @@ __global__ __launch_bounds__(THR, 1) void conv3_kernel(Pro pa, const bf16_t* __r
   }
 }
 
-template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM, int SCHED>
+template <int C, int BN, int TH, int W, int PRO, bool FLIP, int WM, int SCHED, int FEED>
 hipError_t launch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, int H, int N, hipStream_t st) {
   const int nsl = N / BN;
   const int tiles = Nimg * (H / TH);
@@ -322,8 +362,8 @@ hipError_t launch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, 
   if (per_xcd < 1) per_xcd = 1;
   const int need = ceil_div(tiles, 8);
   if (per_xcd > need) per_xcd = need;
-  hipLaunchKernelGGL((conv3_kernel<C, BN, TH, W, PRO, FLIP, WM, SCHED>), dim3(8 * nsl * per_xcd), dim3(THR), 0, st, pa, w,
-                     E, H, N, tiles, nsl);
+  hipLaunchKernelGGL((conv3_kernel<C, BN, TH, W, PRO, FLIP, WM, SCHED, FEED>), dim3(8 * nsl * per_xcd), dim3(THR), 0, st,
+                     pa, w, E, H, N, tiles, nsl);
   return hipGetLastError();
 }
 
@@ -335,12 +375,12 @@ inline int pick_th(int C, int N, int W, int pro) {
   return 0;
 }
 
-template <int PRO, bool FLIP, int SCHED>
+template <int PRO, bool FLIP, int SCHED, int FEED>
 hipError_t dispatch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, int H, int W, int C, int N,
                     hipStream_t st) {
   if (C == 64 && N == 64 && W == 56) {
-    if constexpr (PRO == 2) return launch<64, 64, 4, 56, PRO, FLIP, 2, SCHED>(pa, w, E, Nimg, H, N, st);
-    else return launch<64, 64, 8, 56, PRO, FLIP, 4, SCHED>(pa, w, E, Nimg, H, N, st);
+    if constexpr (PRO == 2) return launch<64, 64, 4, 56, PRO, FLIP, 2, SCHED, FEED>(pa, w, E, Nimg, H, N, st);
+    else return launch<64, 64, 8, 56, PRO, FLIP, 4, SCHED, FEED>(pa, w, E, Nimg, H, N, st);
   }
   return hipErrorInvalidValue;
 }
@@ -374,11 +414,18 @@ hipError_t dispatch(const Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg
 //    offset at issue; the 36 (piece, tap) addresses, and the staging coordinates, were what the
 //    predecessor precomputed ahead of the loop and spilled. Fragment reads are pinned as above;
 //  * SCHED 0: `#pragma unroll 1` tap loop, vmcnt(0) at every tap and before tap 0, the next
-//    tile's halo issued after the tap loop (it flies under the epilogue only).
+//    tile's halo issued after the tap loop (it flies under the epilogue only);
+//  * FEED 1 (as above): the thread's first three by / bmask rows are loaded in taps 6, 7 and 8,
+//    which issue no halo loads, one row (always two loads: the zero page for a row past the
+//    tensor) per tap after that tap's filter DMA, so the wait ending those taps is vmcnt(2) by
+//    the same in-order argument; the other four rows follow stage_acc. The compiler counts the
+//    feeding loads itself in the epilogue; the DMA it does not see is older than all of them, so
+//    its waits only get stronger.
 //
 // Resources (as above), SCHED 1 / SCHED 0, LDS 159,744 B, 0 AGPRs, 2 waves/SIMD:
-//   conv3s_kernel<128,128,8,28,28,PRO 0,fwd|flip>  239 VGPR, scratch 0  / 256 VGPR, scratch 144 B
-//   conv3s_kernel<128,128,8,28,28,PRO 1,fwd>       245 VGPR, scratch 0  / 256 VGPR, scratch 276 B
+//   conv3s_kernel<128,128,8,28,28,PRO 0,fwd|flip>     219 VGPR, scratch 0  / 256 VGPR, scratch 144 B
+//   conv3s_kernel<128,128,8,28,28,PRO 0,flip,FEED 1>  228 VGPR, scratch 0
+//   conv3s_kernel<128,128,8,28,28,PRO 1,fwd>          226 VGPR, scratch 0  / 256 VGPR, scratch 276 B
 namespace c3s {
 
 constexpr int THR = 512;
@@ -412,7 +459,7 @@ __device__ __forceinline__ void wait_vm_upto(int n) {
   }
 }
 
-template <int C, int BN, int TR, int H, int W, int PRO, bool FLIP, int SCHED>
+template <int C, int BN, int TR, int H, int W, int PRO, bool FLIP, int SCHED, int FEED>
 __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t* __restrict__ w, EpiParams E,
                                                        int rows_total, int N, int tiles) {
   constexpr int WM = 2, WN = NW / WM;
@@ -570,6 +617,18 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
     }
   };
 
+  // epilogue mapping: a thread owns 16-B column chunk tid % ECPR of rows tid / ECPR + k * RPP
+  constexpr int ECPR = BN / 8;
+  constexpr int RPP = THR / ECPR;
+  constexpr int NR = (BM + RPP - 1) / RPP;
+  // FEED 1 (as in the kernel above): prefetched feeding epilogue (stream_epi.h). by / bmask of the
+  // thread's rows 0 .. FA - 1 are loaded under taps FTAP .. 8, one row (two loads) per tap, each
+  // after that tap's filter DMA; rows FA .. NR - 1 after stage_acc, when the accumulators are dead
+  constexpr int FA = 3, FTAP = 9 - FA;
+  static_assert(NR > FA, "two batches");
+  static_assert(FEED == 0 || (FLIP && SCHED != 0), "feeding epilogue: data gradients under SCHED 1");
+  const int M = rows_total * W;
+
   int bcur = 0;
   int t = g;
   if (t < tiles) {
@@ -593,6 +652,8 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
     if constexpr (SCHED == 0) wait_vm<0>();
     __syncthreads();
     const bool more = t + G < tiles;
+    sepi::FeedBatch<1> fa[FA];  // (declared per tile: not carried around the tile loop)
+    sepi::FeedBatch<NR - FA> fb;
     f32x4_t acc[TM][TN];
 #pragma unroll
     for (int a = 0; a < TM; ++a)
@@ -606,6 +667,8 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
     // the wait is vmcnt(0).
     constexpr int HPT = 2;
     static_assert(HPT * 8 >= NA, "the halo loads are all retired by the wait of the last tap");
+    static_assert(HPT * FTAP >= NA, "no tap issues both halo and feeding loads (wait_vm_upto takes 0 .. 3)");
+    const int m0 = t * BM;
     const Geo qn = geo(SCHED != 0 && more ? t + G : t);
 #pragma unroll(SCHED != 0 ? 9 : 1)
     for (int tap = 0; tap < 9; ++tap) {
@@ -618,6 +681,15 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
           const int ft = c3::fresh<SCHED>(tid);
 #pragma unroll
           for (int i = h0; i < h1; ++i) load_slot(qn, ft, i);
+        }
+      }
+      // feeding epilogue: this tile's by / bmask row tap - FTAP of the thread, also after the DMA
+      // and always two loads (taps FTAP .. 8 issue no halo loads: static_assert above)
+      const int nfeed = (FEED != 0 && tap >= FTAP) ? 2 : 0;
+      if constexpr (FEED != 0) {
+        if (tap >= FTAP) {
+          const int ft = c3::fresh<SCHED>(tid);
+          sepi::feed_batch_load<BM, RPP, 1>(fa[tap - FTAP], E, tap - FTAP, ft / ECPR, m0, M, (ft % ECPR) * 8);
         }
       }
       const char* sBc = sBb + bcur * SBT;
@@ -644,23 +716,27 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
           for (int c = 0; c < TN; ++c) acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c], af[a], acc[a][c], 0, 0, 0);
         c3::frag_fence<SCHED>();
       }
-      if constexpr (SCHED != 0) wait_vm_upto(more ? h1 - h0 : 0);  // the next tap's DMA landed (see above)
-      else wait_vm<0>();                                           // the next tap's DMA landed
+      // SCHED 1: what this tap issued after its DMA stays in flight, everything older is retired:
+      // the halo loads (h1 - h0 = HPT in taps 0 .. NA / HPT - 1, with a next tile) or the two
+      // feeding loads (taps FTAP .. 8, FEED 1), never both. So a feeding row issued
+      // in tap k is retired by the wait of tap k + 1, the last one by the epilogue's own waits
+      // (the compiler counts those loads; the DMA it does not see is older than all of them)
+      if constexpr (SCHED != 0) wait_vm_upto((more ? h1 - h0 : 0) + nfeed);
+      else wait_vm<0>();  // the next tap's DMA landed
       __syncthreads();
       bcur = bnext;
     }
     // (the last barrier above: every wave is done reading the halo) stage the tile over it
+    const int fe = c3::fresh<SCHED>(tid);  // (the row addresses of the epilogue are not held across the tile loop either)
+    const int c = fe % ECPR, r0 = fe / ECPR;
+    const int n = c * 8;
     sepi::stage_acc<TM, TN, WR, WC, PITCH>(sA, acc, wm, wn, lane, epi_alpha(E));
+    if constexpr (FEED != 0) sepi::feed_batch_load<BM, RPP, NR - FA>(fb, E, FA, r0, m0, M, n);
     // SCHED 0: the next tile's halo into registers now that the accumulators are dead: it flies
     // under this tile's epilogue only
     if constexpr (SCHED == 0)
       if (more) load_tile(t + G);
     __syncthreads();
-    constexpr int ECPR = BN / 8;
-    constexpr int RPP = THR / ECPR;
-    const int m0 = t * BM;
-    const int c = tid % ECPR, r0 = tid / ECPR;
-    const int n = c * 8;
     const bool vst = (E.ldo & 7) == 0;
     float bias8[8], s8[8], q8[8], r8[8];
 #pragma unroll
@@ -668,8 +744,11 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
       bias8[j] = E.bias ? E.bias[n + j] : 0.f;
       s8[j] = q8[j] = r8[j] = 0.f;
     }
-    const int M = rows_total * W;
-    if (E.beta || E.residual || E.by)
+    if constexpr (FEED != 0) {
+#pragma unroll
+      for (int k = 0; k < FA; ++k) sepi::feed_batch_rows<BM, RPP, PITCH, 1>(fa[k], E, sA, k, c, r0, m0, M, n, s8, q8);
+      sepi::feed_batch_rows<BM, RPP, PITCH, NR - FA>(fb, E, sA, FA, c, r0, m0, M, n, s8, q8);
+    } else if (E.beta || E.residual || E.by)
       epi_rows<BM, RPP, PITCH, true, 2>(E, sA, c, r0, n, m0, M, N, vst, vst, bias8, s8, q8, r8);
     else
       epi_rows<BM, RPP, PITCH, false>(E, sA, c, r0, n, m0, M, N, vst, vst, bias8, s8, q8, r8);
@@ -682,7 +761,7 @@ __global__ __launch_bounds__(THR, 1) void conv3s_kernel(c3::Pro pa, const bf16_t
   }
 }
 
-template <int PRO, bool FLIP, int SCHED>
+template <int PRO, bool FLIP, int SCHED, int FEED>
 hipError_t launch(const c3::Pro& pa, const bf16_t* w, const EpiParams& E, int Nimg, int N, hipStream_t st) {
   const int rows = Nimg * 28;
   const int tiles = ceil_div(rows, 8);
@@ -690,8 +769,8 @@ hipError_t launch(const c3::Pro& pa, const bf16_t* w, const EpiParams& E, int Ni
   if (G < 8) G = 8;
   const int need = ceil_div(tiles, 8) * 8;
   if (G > need) G = need;
-  hipLaunchKernelGGL((conv3s_kernel<128, 128, 8, 28, 28, PRO, FLIP, SCHED>), dim3(G), dim3(THR), 0, st, pa, w, E, rows,
-                     N, tiles);
+  hipLaunchKernelGGL((conv3s_kernel<128, 128, 8, 28, 28, PRO, FLIP, SCHED, FEED>), dim3(G), dim3(THR), 0, st, pa, w, E,
+                     rows, N, tiles);
   return hipGetLastError();
 }
 
@@ -714,7 +793,19 @@ int& conv3_sched_flag() {
   static int on = getenv_int("TTD_CONV3_SCHED", 1);  // 1: the schedule described above; 0: its predecessor (A/B)
   return on;
 }
+int& conv3_feed_flag() {
+  static int on = getenv_int("TTD_CONV3_FEED", 1);  // 1: prefetched feeding epilogue of the data gradients (FEED 1); 0: epi_rows
+  return on;
+}
 }  // namespace
+
+// Runtime switch of the prefetched feeding-BN epilogue of the halo data gradients (stream_epi.h:
+// feed_batch_*; 0 = the generic row loop); returns the previous setting. Results are bit-identical.
+TTDK_EXPORT int ttdk_set_conv3_feed(int on) {
+  const int old = conv3_feed_flag();
+  conv3_feed_flag() = on ? 1 : 0;
+  return old;
+}
 
 // Runtime switch between the two schedules of both halo kernels (template parameter SCHED);
 // returns the previous setting. Results are bit-identical under both.
@@ -752,9 +843,11 @@ TTDK_EXPORT int ttdk_conv3_halo(const bf16_t* x, const bf16_t* x2, const uint8_t
     if (pro == 1 && (!s || !b)) return hipErrorInvalidValue;
     if (side_mask && pro != 1) return hipErrorInvalidValue;
     const c3::Pro pa{x, nullptr, nullptr, s, b, side, side_mask};
+    if (pro == 0 && flip && sched && conv3_feed_flag() && sepi::feed_case(e))
+      return c3s::launch<0, true, 1, 1>(pa, w, e, Nimg, N, st);
 #define C3S_CASE(P_, F_)              \
   if (pro == P_ && (flip != 0) == F_) \
-    return sched ? c3s::launch<P_, F_, 1>(pa, w, e, Nimg, N, st) : c3s::launch<P_, F_, 0>(pa, w, e, Nimg, N, st);
+    return sched ? c3s::launch<P_, F_, 1, 0>(pa, w, e, Nimg, N, st) : c3s::launch<P_, F_, 0, 0>(pa, w, e, Nimg, N, st);
     C3S_CASE(0, false)
     C3S_CASE(0, true)
     C3S_CASE(1, false)
@@ -769,10 +862,14 @@ TTDK_EXPORT int ttdk_conv3_halo(const bf16_t* x, const bf16_t* x2, const uint8_t
   if (pro == 2 && (!s || !x2)) return hipErrorInvalidValue;
   if (side_mask && pro != 1) return hipErrorInvalidValue;
   const c3::Pro pa{x, x2, mask_in, s, b, side, side_mask};
-#define C3_CASE(P_, F_)                                                           \
-  if (pro == P_ && (flip != 0) == F_)                                             \
-    return sched ? c3::dispatch<P_, F_, 1>(pa, w, e, Nimg, H, W, C, N, st)        \
-                 : c3::dispatch<P_, F_, 0>(pa, w, e, Nimg, H, W, C, N, st);
+  if (flip && sched && conv3_feed_flag() && sepi::feed_case(e)) {  // (N == BN: full slices)
+    if (pro == 0) return c3::dispatch<0, true, 1, 1>(pa, w, e, Nimg, H, W, C, N, st);
+    if (pro == 2) return c3::dispatch<2, true, 1, 1>(pa, w, e, Nimg, H, W, C, N, st);
+  }
+#define C3_CASE(P_, F_)                                                        \
+  if (pro == P_ && (flip != 0) == F_)                                          \
+    return sched ? c3::dispatch<P_, F_, 1, 0>(pa, w, e, Nimg, H, W, C, N, st)  \
+                 : c3::dispatch<P_, F_, 0, 0>(pa, w, e, Nimg, H, W, C, N, st);
   C3_CASE(0, false)
   C3_CASE(1, false)
   C3_CASE(0, true)

@@ -307,6 +307,16 @@ def set_conv3_sched(new: bool) -> bool:
     return bool(_lib.query("ttdk_set_conv3_sched", 1 if new else 0))
 
 
+_lib.register({"ttdk_set_conv3_feed": [_lib.I]})
+
+
+def set_conv3_feed(new: bool) -> bool:
+    """Switch the data gradients of both halo 3x3 kernels between the prefetched feeding-BN
+    epilogue and the generic row loop (TTD_CONV3_FEED; an A/B switch: results are bit-identical;
+    the prefetched form exists under set_conv3_sched(True) only); returns the previous setting."""
+    return bool(_lib.query("ttdk_set_conv3_feed", 1 if new else 0))
+
+
 def conv3_rows(H, W, C, N, pro=0):
     """Output pixels per tile of the halo 3x3 kernel (conv3_halo.hip) for a [*, H, W, C] -> N
     3x3/s1/p1 conv with prologue `pro` (0 none, 1 BN forward, 2 BN backward), or 0 when the

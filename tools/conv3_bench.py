@@ -1,16 +1,24 @@
 #!/usr/bin/env python3
 """A/B of the halo 3x3 kernels (conv3_halo.hip), interleaved rounds in one process, median us.
 
-Part 1, both schedules of the kernels (ops.gemm.set_conv3_sched: old = the predecessor, new) on
-the launches the ResNet-50 step runs, at stage 2 (56x56, 64 -> 64) and stage 3 (28x28, 128 -> 128):
+Part 1, three arms of the kernels, interleaved per variant and round:
+
+  sched0   the predecessor schedule                      set_conv3_sched(0)
+  feed0    the current schedule, generic epilogue        set_conv3_sched(1), set_conv3_feed(0)
+  new      the current schedule, prefetched feeding-BN   set_conv3_sched(1), set_conv3_feed(1)
+           epilogue of the data gradients
+
+on the launches the ResNet-50 step runs, at stage 2 (56x56, 64 -> 64) and stage 3 (28x28, 128 -> 128):
 
   fwdbn_c3   BN apply + ReLU prologue, conv, BN statistics     conv3_halo(bn_fwd, stat)
   dg_c3      data gradient with the feeding-BN epilogue        conv3_halo(flip, bn_stat)
   dgrad_c3   (stage 2) the same with the BN backward as prologue (TTD_C3_DGRAD=1)
 
-with, per variant and schedule: median us, max - min over the rounds, us per tile per workgroup,
+with, per variant and arm: median us, max - min over the rounds, us per tile per workgroup,
 and the two per-tile floors from the shapes (MFMA: 4096 bf16 FLOP/clk/CU at 2.4 GHz; HBM: the
-tile's halo, output, side tensors and bits at a 1/CUs share of 5 TB/s).
+tile's halo, output, side tensors and bits at a 1/CUs share of 5 TB/s), and feed0 -> new judged by
+the rule "faster when the new median is below the old one by more than three times the larger
+max - min spread of the two arms".
 
 Part 2 (stage 2, as before): the halo kernel against the paths it replaces
 
@@ -96,34 +104,44 @@ def main():
                 lambda t=t: G.conv3_halo(t["g"], t["wt"], flip=True, prologue=("bn_bwd", t["y"], None, t["coef"], t["dz"]),
                                          bn_stat=(t["fy"], t["fm"])),
                 r4, 2 * halo(r4, r4) + r4 * W * (3 * px + px / 16))        # g, y halos; fy, bits in; dz, out
-    res = {(k, s): [] for k in sched for s in (0, 1)}
+    arms = (("sched0", False, False), ("feed0", True, False), ("new", True, True))  # (label, sched, feed)
+    res = {(k, a[0]): [] for k in sched for a in arms}
     prev = G.set_conv3_sched(True)
+    prev_feed = G.set_conv3_feed(True)
     for _ in range(args.rounds):
         for k, (fn, _, _) in sched.items():
-            for s in (0, 1):
-                G.set_conv3_sched(bool(s))
+            for label, s, f in arms:
+                G.set_conv3_sched(s)
+                G.set_conv3_feed(f)
                 fn()
-                res[(k, s)].append(timeit(fn))
+                res[(k, label)].append(timeit(fn))
     G.set_conv3_sched(prev)
-    print("%-5s %-9s %-5s %9s %8s %12s %10s %9s %7s" % ("stage", "variant", "sched", "median us", "max-min", "us/tile/wg",
+    G.set_conv3_feed(prev_feed)
+    print("%-5s %-9s %-6s %9s %8s %12s %10s %9s %7s" % ("stage", "variant", "arm", "median us", "max-min", "us/tile/wg",
                                                            "MFMA floor", "HBM floor", "TF/s"))
-    tot = {0: 0.0, 1: 0.0}
+    tot = {a[0]: 0.0 for a in arms}
     for (stage, name), (_, rows, nbytes) in sched.items():
         H, W, C = {2: (56, 56, 64), 3: (28, 28, 128)}[stage]
         tiles = -(-B * H // rows)
         per_wg = -(-tiles // wgs)
         f_mfma = 2.0 * rows * W * C * 9 * C / MFMA_FLOP_PER_CLK_CU / CLK_HZ * 1e6
         f_hbm = nbytes / (HBM_BPS / cus) * 1e6
-        for s in (0, 1):
-            v = res[((stage, name), s)]
+        for label, _, _ in arms:
+            v = res[((stage, name), label)]
             med = statistics.median(v)
             if name != "dgrad_c3":
-                tot[s] += med
-            print("%-5d %-9s %-5s %9.1f %8.1f %12.2f %10.2f %9.2f %7.0f" % (
-                stage, name, ("old", "new")[s], med, max(v) - min(v), med / per_wg, f_mfma, f_hbm,
+                tot[label] += med
+            print("%-5d %-9s %-6s %9.1f %8.1f %12.2f %10.2f %9.2f %7.0f" % (
+                stage, name, label, med, max(v) - min(v), med / per_wg, f_mfma, f_hbm,
                 2.0 * B * H * W * C * 9 * C / med / 1e6), flush=True)
-    print("sum of the four in-step variants (fwdbn_c3, dg_c3 at both stages): old %.1f us, new %.1f us" % (tot[0], tot[1]),
-          flush=True)
+        o, nw = res[((stage, name), "feed0")], res[((stage, name), "new")]
+        gain = statistics.median(o) - statistics.median(nw)
+        spread = max(max(o) - min(o), max(nw) - min(nw))
+        print("%-5d %-9s feed0 -> new: %+.1f us, spread %.1f us: %s" % (
+            stage, name, -gain, spread, "faster" if gain > 3 * spread else "slower" if -gain > spread else "same"),
+            flush=True)
+    print("sum of the four in-step variants (fwdbn_c3, dg_c3 at both stages): " +
+          ", ".join("%s %.1f us" % (a[0], tot[a[0]]) for a in arms), flush=True)
     if args.no_paths:
         return
 
