@@ -263,6 +263,74 @@ class Conv2D(Layer):
         return self.activation(y) if self.activation is not None else y
 
 
+class DepthwiseConv2D(Layer):
+    """NHWC depthwise conv; depthwise_kernel [R, S, C, depth_multiplier] (Keras' name and layout),
+    output channel c * depth_multiplier + m."""
+    _default_name = "depthwise_conv2d"
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="same", depth_multiplier=1, activation=None,
+                 use_bias=True, depthwise_initializer="glorot_uniform", bias_initializer="zeros",
+                 depthwise_regularizer=None, name=None):
+        super().__init__(name)
+        self.kernel_size = (kernel_size, kernel_size) if isinstance(kernel_size, int) else tuple(kernel_size)
+        self.strides = (strides, strides) if isinstance(strides, int) else tuple(strides)
+        self.padding = padding.upper()
+        self.depth_multiplier = int(depth_multiplier)
+        self.activation = _act(activation)
+        self.use_bias = use_bias
+        self.depthwise_initializer, self.bias_initializer = depthwise_initializer, bias_initializer
+        self.depthwise_regularizer = depthwise_regularizer
+
+    def _out_channels(self, input_shape):
+        return input_shape[-1] * self.depth_multiplier
+
+    def build(self, input_shape):
+        self.add_weight("depthwise_kernel", self.kernel_size + (input_shape[-1], self.depth_multiplier),
+                        self.depthwise_initializer, self.depthwise_regularizer)
+        self._build_rest(input_shape)
+        if self.use_bias:
+            self.add_weight("bias", (self._out_channels(input_shape),), self.bias_initializer)
+        else:
+            self.bias = None
+        super().build(input_shape)
+
+    def _build_rest(self, input_shape):
+        pass
+
+    def _conv(self, x):
+        return N.depthwise_conv2d(x, self.depthwise_kernel, self.strides, self.padding)
+
+    def call(self, x, **kw):
+        y = self._conv(x)
+        if self.bias is not None:
+            y = N.bias_add(y, self.bias)
+        return self.activation(y) if self.activation is not None else y
+
+
+class SeparableConv2D(DepthwiseConv2D):
+    """Depthwise conv, then a 1x1 conv to `filters` channels: depthwise_kernel [R, S, C, M],
+    pointwise_kernel [1, 1, C*M, filters], bias [filters]."""
+    _default_name = "separable_conv2d"
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="same", depth_multiplier=1, activation=None,
+                 use_bias=True, depthwise_initializer="glorot_uniform", pointwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, pointwise_regularizer=None, name=None):
+        super().__init__(kernel_size, strides, padding, depth_multiplier, activation, use_bias,
+                         depthwise_initializer, bias_initializer, depthwise_regularizer, name)
+        self.filters = int(filters)
+        self.pointwise_initializer, self.pointwise_regularizer = pointwise_initializer, pointwise_regularizer
+
+    def _out_channels(self, input_shape):
+        return self.filters
+
+    def _build_rest(self, input_shape):
+        self.add_weight("pointwise_kernel", (1, 1, input_shape[-1] * self.depth_multiplier, self.filters),
+                        self.pointwise_initializer, self.pointwise_regularizer)
+
+    def _conv(self, x):
+        return N.separable_conv2d(x, self.depthwise_kernel, self.pointwise_kernel, self.strides, self.padding)
+
+
 class BatchNormalization(Layer):
     """Over the last (channel) axis; gamma/beta trainable, moving_mean/variance not."""
     _default_name = "batch_normalization"

@@ -9,8 +9,8 @@ silent GPU fallback to torch compute: a GPU input the kernels cannot take (dtype
 fp32/bf16, an unsupported attention head size) raises InvalidArgumentError.
 
 GPU precision: fp32 inputs stay fp32 for dense/matmul (exact-fp32 MFMA, gemm_f32.hip),
-normalisation, pooling, embeddings, activations and losses (nn_generic.hip / elementwise.hip /
-xent.hip); bf16 inputs use the bf16 MFMA engines. conv2d and attention compute in bf16 (fp32
+normalisation, pooling, depthwise convolution, embeddings, activations and losses (nn_generic.hip /
+depthwise.hip / elementwise.hip / xent.hip); bf16 inputs use the bf16 MFMA engines. conv2d and attention compute in bf16 (fp32
 accumulation) for either input dtype.
 
     ttd.nn.elu(x); ttd.nn.dropout(x, rate=0.01)
@@ -18,6 +18,8 @@ accumulation) for either input dtype.
     ttd.nn.in_top_k(z, y, 1); ttd.nn.layer_norm(x, gamma, beta)
     ttd.nn.dense(x, kernel, bias, activation="relu")      # kernel [in, out] (TF layout)
     ttd.nn.conv2d(x, kernel, strides, padding)            # NHWC, kernel [R, S, C, K]
+    ttd.nn.depthwise_conv2d(x, kernel, strides, padding, dilations)   # kernel [R, S, C, M], R, S <= 7
+    ttd.nn.separable_conv2d(x, depthwise_kernel, pointwise_kernel)    # depthwise, then the 1x1 GEMM
     ttd.nn.attention(q, k, v, num_heads, dropout_rate)    # [B, S, H*64] token-major
     ttd.nn.attention(q, k, v, 16, num_kv_heads=4)         # grouped-query: k, v [B, Sk, 4*64]
     ttd.nn.rotary_embedding(q, 16, offset=0)              # RoPE on q / k before attention
@@ -707,6 +709,92 @@ def _pair(v):
     if len(v) == 4:  # TF NHWC [1, kh, kw, 1]
         return v[1], v[2]
     return v[0], v[1]
+
+
+class _DepthwiseConv2D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel, geom):
+        from .ops import kernels as K
+        xc = x.contiguous()
+        wf = kernel.float().contiguous()  # the kernels take the (tiny) filter as fp32
+        y = K.dwconv_fwd(xc, wf, geom)
+        ctx.save_for_backward(xc, wf)
+        ctx.cfg = (geom, kernel.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import kernels as K
+        xc, wf = ctx.saved_tensors
+        geom, wdt = ctx.cfg
+        d = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[1]:
+            dw = K.dwconv_wgrad(xc, d, tuple(wf.shape), geom).to(wdt)
+        if ctx.needs_input_grad[0]:
+            dx = K.dwconv_dgrad(d, wf, tuple(xc.shape), geom)
+        return dx, dw, None
+
+
+def _dw_geometry(H, W, R, S, strides, padding, dilations):
+    """(sh, sw, ph, pw, dh, dw, P, Q) of a depthwise conv: TF 'SAME' (the extra row / column goes
+    to the bottom / right) / 'VALID', or explicit symmetric (ph, pw)."""
+    (sh, sw), (dh, dw) = strides, dilations
+    Re, Se = (R - 1) * dh + 1, (S - 1) * dw + 1  # dilated filter extent
+    if isinstance(padding, str):
+        if padding.upper() == "VALID":
+            ph, pw, P, Q = 0, 0, (H - Re) // sh + 1, (W - Se) // sw + 1
+        elif padding.upper() == "SAME":
+            P, Q = -(-H // sh), -(-W // sw)
+            ph, pw = max((P - 1) * sh + Re - H, 0) // 2, max((Q - 1) * sw + Se - W, 0) // 2
+        else:
+            raise InvalidArgumentError("padding must be 'SAME', 'VALID' or (ph, pw), got %r" % (padding,))
+    else:
+        ph, pw = _pair(padding)
+        P, Q = (H + 2 * ph - Re) // sh + 1, (W + 2 * pw - Se) // sw + 1
+    if P <= 0 or Q <= 0 or min(sh, sw, dh, dw) <= 0 or ph < 0 or pw < 0:
+        raise InvalidArgumentError("depthwise_conv2d: empty output or bad strides / dilations / padding "
+                                   "(input %dx%d, filter %dx%d)" % (H, W, R, S))
+    return sh, sw, ph, pw, dh, dw, P, Q
+
+
+def depthwise_conv2d(x, kernel, strides=(1, 1), padding="SAME", dilations=(1, 1)):
+    """tf.nn.depthwise_conv2d: NHWC x [N,H,W,C], kernel [R,S,C,M] (R, S <= 7), output [N,P,Q,C*M]
+    where channel c*M+m is input channel c filtered by kernel[:, :, c, m]. padding 'SAME' | 'VALID'
+    | (ph, pw); strides / dilations an int, a pair or TF's [1, a, b, 1]. On the GPU fp32 stays
+    fp32, bf16 accumulates in fp32, and the kernel's gradient is bitwise reproducible."""
+    if x.dim() != 4 or kernel.dim() != 4:
+        raise InvalidArgumentError("depthwise_conv2d takes x [N,H,W,C] and kernel [R,S,C,M], got %s and %s"
+                                   % (tuple(x.shape), tuple(kernel.shape)))
+    R, S, C, M = kernel.shape
+    if C != x.shape[3]:
+        raise InvalidArgumentError("depthwise_conv2d: kernel has %d input channels, x has %d" % (C, x.shape[3]))
+    if R > 7 or S > 7:
+        raise InvalidArgumentError("depthwise_conv2d: filters up to 7x7, got %dx%d" % (R, S))
+    geom = _dw_geometry(x.shape[1], x.shape[2], R, S, _pair(strides), padding, _pair(dilations))
+    if _on_gpu(x, kernel):
+        return _DepthwiseConv2D.apply(x, kernel, geom)
+    sh, sw, ph, pw, dh, dw, P, Q = geom
+    # explicit zero padding (covers SAME's extra bottom / right row) then an unpadded grouped conv
+    eh = max((P - 1) * sh + (R - 1) * dh + 1 - x.shape[1] - ph, 0)
+    ew = max((Q - 1) * sw + (S - 1) * dw + 1 - x.shape[2] - pw, 0)
+    xp = F.pad(x.float().permute(0, 3, 1, 2), (pw, ew, ph, eh))
+    wk = kernel.float().permute(2, 3, 0, 1).reshape(C * M, 1, R, S)
+    y = F.conv2d(xp, wk, stride=(sh, sw), dilation=(dh, dw), groups=C)
+    return y[:, :, :P, :Q].permute(0, 2, 3, 1).to(x.dtype)
+
+
+def separable_conv2d(x, depthwise_kernel, pointwise_kernel, strides=(1, 1), padding="SAME", dilations=(1, 1)):
+    """tf.nn.separable_conv2d: depthwise_conv2d with depthwise_kernel [R,S,C,M], then conv2d with
+    pointwise_kernel [1,1,C*M,K] (a plain GEMM)."""
+    if pointwise_kernel.dim() != 4 or tuple(pointwise_kernel.shape[:2]) != (1, 1):
+        raise InvalidArgumentError("separable_conv2d: pointwise_kernel must be [1,1,C*M,K], got %s"
+                                   % (tuple(pointwise_kernel.shape),))
+    y = depthwise_conv2d(x, depthwise_kernel, strides, padding, dilations)
+    if pointwise_kernel.shape[2] != y.shape[3]:
+        raise InvalidArgumentError("separable_conv2d: pointwise_kernel takes %d channels, the depthwise output has %d"
+                                   % (pointwise_kernel.shape[2], y.shape[3]))
+    return conv2d(y, pointwise_kernel, (1, 1), "VALID")
 
 
 def _pool_geometry(H, W, k, s, padding):

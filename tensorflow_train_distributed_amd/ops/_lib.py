@@ -43,8 +43,15 @@ class ConvGeom(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "H", "W", "C", "K", "R", "S", "P", "Q", "sh", "sw", "ph", "pw", "dh", "dw")]
 
 
+class DwConvGeom(ctypes.Structure):
+    """Mirror of ``TtdkDwConv`` (dwconv_plan.h): input NHWC [N,H,W,C], filter [R,S,C,M], output [N,P,Q,C*M]."""
+
+    _fields_ = [(n, c_int) for n in ("N", "H", "W", "C", "M", "R", "S", "P", "Q", "sh", "sw", "ph", "pw", "dh", "dw")]
+
+
 E = ctypes.POINTER(Epilogue)
 G = ctypes.POINTER(ConvGeom)
+DG = ctypes.POINTER(DwConvGeom)
 
 # name -> argtypes (restype is always int = hipError_t). Structs are passed by reference.
 _SIGS = {
@@ -150,7 +157,8 @@ def register(sigs: dict):
 
 _RESTYPE = {"ttdk_colsum_ws_floats": c_longlong,
             "ttdk_gemm_wgrad_bias_ws": c_longlong, "ttdk_gemm4t_ws": c_longlong,
-            "ttdk_conv_wgrad4t_ws": c_longlong, "ttdk_conv_wgrad4t8_ws": c_longlong}
+            "ttdk_conv_wgrad4t_ws": c_longlong, "ttdk_conv_wgrad4t8_ws": c_longlong,
+            "ttdk_dwconv_wgrad_ws_floats": c_longlong}
 
 
 def fn(name):

@@ -10,7 +10,7 @@ from collections import namedtuple
 from ctypes import c_int, c_longlong
 
 from .. import _native
-from ._lib import ConvGeom, G
+from ._lib import DG, ConvGeom, DwConvGeom, G
 
 _PI = ctypes.POINTER(c_int)
 _TAKES = ("conv_fwd4w", "conv_dgrad4w", "conv_fwd4k8", "conv_dgrad4k8", "conv_wgrad_fp8", "conv_wgrad_bn",
@@ -29,6 +29,19 @@ _SIGS = {
     "gemm4t_takes": (c_int, [c_longlong] * 3),
 }
 _SIGS.update({n + "_takes": (c_int, [G]) for n in _TAKES})
+_PL = ctypes.POINTER(c_longlong)
+# depthwise convolution (csrc/kernels/dwconv_plan.h), exported as ttd_dwplan_*
+_DW_SIGS = {
+    "geom_size": (c_int, []),
+    "valid": (c_int, [DG]),
+    "fast_takes": (c_int, [DG, c_int]),
+    "strip": (c_int, []),
+    "max_slabs": (c_int, []),
+    "wgrad_parts": (c_int, [DG]),
+    "slab_rows": (None, [DG, c_int, _PL, _PL]),
+    "part_stride": (c_longlong, [DG]),
+    "wgrad_ws_floats": (c_longlong, [DG]),
+}
 
 _fns = {}
 
@@ -90,3 +103,66 @@ big_bn, big_bn_wgrad, g4t_bm, clamp_splits, clamp_splits_4t, gemm4t_takes = map(
 
 def subpixel_stat_rows(g):
     return _fn("subpixel_stat_rows")(ctypes.byref(g))
+
+
+# ------------------------------------------------------------------ depthwise convolution
+_dw_fns = {}
+
+
+def _dw(name):
+    if not _dw_fns:
+        lib = _native.rt()
+        for n, (res, args) in _DW_SIGS.items():
+            f = getattr(lib, "ttd_dwplan_" + n)
+            f.restype, f.argtypes = res, args
+            _dw_fns[n] = f
+        if _dw_fns["geom_size"]() != ctypes.sizeof(DwConvGeom):
+            raise RuntimeError("ops._lib.DwConvGeom (%d bytes) does not match TtdkDwConv (%d bytes)"
+                               % (ctypes.sizeof(DwConvGeom), _dw_fns["geom_size"]()))
+    return _dw_fns[name]
+
+
+def dw_geom(x_shape, w_shape, sh, sw, ph, pw, dh, dw, P, Q):
+    """DwConvGeom of input [N,H,W,C] and filter [R,S,C,M]."""
+    N, H, W, C = (int(v) for v in x_shape)
+    R, S, _, M = (int(v) for v in w_shape)
+    return DwConvGeom(N, H, W, C, M, R, S, int(P), int(Q), int(sh), int(sw), int(ph), int(pw), int(dh), int(dw))
+
+
+def dw_valid(g) -> bool:
+    return bool(_dw("valid")(ctypes.byref(g)))
+
+
+def dw_fast_takes(g, bf16: bool) -> bool:
+    """Whether the fast form admits geometry g, as far as shape and dtype decide (the launchers
+    also want 16-byte aligned bases)."""
+    return bool(_dw("fast_takes")(ctypes.byref(g), 1 if bf16 else 0))
+
+
+def dw_strip() -> int:
+    """Output columns a fast-form thread produces."""
+    return _dw("strip")()
+
+
+def dw_max_slabs() -> int:
+    return _dw("max_slabs")()
+
+
+def dw_wgrad_parts(g) -> int:
+    """Slabs T of the weight gradient's N*P output rows."""
+    return _dw("wgrad_parts")(ctypes.byref(g))
+
+
+def dw_slab_rows(g, t):
+    """[r0, r1) of slab t."""
+    r0, r1 = c_longlong(), c_longlong()
+    _dw("slab_rows")(ctypes.byref(g), t, r0, r1)
+    return r0.value, r1.value
+
+
+def dw_part_stride(g) -> int:
+    return _dw("part_stride")(ctypes.byref(g))
+
+
+def dw_wgrad_ws_floats(g) -> int:
+    return _dw("wgrad_ws_floats")(ctypes.byref(g))

@@ -3,6 +3,8 @@ cross-entropy, element-wise/layout, optimizers, fp8). All tensors are CUDA tenso
 launch goes to PyTorch's current stream. See the .hip files for the math."""
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -635,6 +637,108 @@ def rms_generic_bwd(dy2d, x2d, gamma, rstd, dgamma, want_dx=True, accumulate=Fal
     _lib.call("ttdk_rms_generic_bwd", dy2d.data_ptr(), x2d.data_ptr(), gamma.data_ptr(), rstd.data_ptr(), _p(dx),
               part.data_ptr(), dgamma.data_ptr(), int(accumulate), _dt(dy2d, x2d), rows, H, _s())
     return dx
+
+
+# ------------------------------------------------------------------ depthwise convolution (depthwise.hip)
+_lib.register({
+    "ttdk_dwconv_fwd": [_lib.P, _lib.P, _lib.P, _lib.I, _lib.DG, _lib.I, _lib.P],
+    "ttdk_dwconv_dgrad": [_lib.P, _lib.P, _lib.P, _lib.I, _lib.DG, _lib.I, _lib.P],
+    "ttdk_dwconv_wgrad": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.I, _lib.DG, _lib.I, _lib.I, _lib.P],
+    "ttdk_dwconv_wgrad_parts": [_lib.DG],
+    "ttdk_dwconv_wgrad_ws_floats": [_lib.DG],
+})
+
+# strides, top / left padding, dilations and the output extent; the bottom / right padding follows
+# from P and Q (TF's SAME: ph = total // 2 with P = ceil(H / sh))
+DwGeom = namedtuple("DwGeom", "sh sw ph pw dh dw P Q")
+_DW_FORMS = {"auto": 0, "generic": 1}
+
+
+def _dw_check(form, geom, x_shape, w_shape, acts, w=None):
+    """Argument checks shared by the three depthwise launchers; returns (form code, dt, DwConvGeom)."""
+    from ..utils.errors import InvalidArgumentError as Bad
+    if form not in _DW_FORMS:
+        raise Bad("depthwise conv: form must be 'auto' or 'generic', got %r" % (form,))
+    if len(x_shape) != 4 or len(w_shape) != 4:
+        raise Bad("depthwise conv: input must be [N,H,W,C] and filter [R,S,C,M], got %s and %s"
+                  % (tuple(x_shape), tuple(w_shape)))
+    if w_shape[2] != x_shape[3]:
+        raise Bad("depthwise conv: filter has %d input channels, the input %d" % (w_shape[2], x_shape[3]))
+    if w_shape[0] > 7 or w_shape[1] > 7:
+        raise Bad("depthwise conv: filters up to 7x7, got %dx%d" % (w_shape[0], w_shape[1]))
+    dt = acts[0].dtype
+    if dt not in _DT:
+        raise Bad("depthwise conv: activations must be float32 or bfloat16, got %s" % dt)
+    for t in acts:
+        if t.dtype != dt:
+            raise Bad("depthwise conv: activations of one dtype per call, got %s and %s" % (dt, t.dtype))
+        if not t.is_cuda or not t.is_contiguous():
+            raise Bad("depthwise conv: tensors must be contiguous and on the GPU")
+    if w is not None and (w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous()
+                          or tuple(w.shape) != tuple(w_shape)):
+        raise Bad("depthwise conv: the filter must be a contiguous float32 GPU tensor [R,S,C,M]")
+    g = _plan.dw_geom(x_shape, w_shape, *DwGeom(*geom))
+    if not _plan.dw_valid(g):
+        raise Bad("depthwise conv: bad geometry %s for input %s, filter %s" % (tuple(geom), tuple(x_shape),
+                                                                              tuple(w_shape)))
+    return _DW_FORMS[form], _DT[dt], g
+
+
+def _dw_out(out, shape, like, what):
+    from ..utils.errors import InvalidArgumentError as Bad
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or not out.is_cuda or not out.is_contiguous():
+        raise Bad("depthwise conv: %s must be a contiguous %s GPU tensor of shape %s" % (what, like.dtype, tuple(shape)))
+    return out
+
+
+def dwconv_fwd(x, w, geom, out=None, form="auto"):
+    """y [N,P,Q,C*M] = depthwise conv of x [N,H,W,C] (bf16 / fp32) with w fp32 [R,S,C,M]; geom is a
+    DwGeom (sh, sw, ph, pw, dh, dw, P, Q). form 'generic' forces the shape-general kernel."""
+    f, dt, g = _dw_check(form, geom, x.shape, w.shape, (x,), w)
+    y = _dw_out(out, (g.N, g.P, g.Q, g.C * g.M), x, "out")
+    _lib.call("ttdk_dwconv_fwd", x.data_ptr(), w.data_ptr(), y.data_ptr(), dt, g, f, _s())
+    return y
+
+
+def dwconv_dgrad(dy, w, x_shape, geom, out=None, form="auto"):
+    """dx [N,H,W,C] from dy [N,P,Q,C*M]; every element of dx is written (no zero fill needed)."""
+    from ..utils.errors import InvalidArgumentError as Bad
+    f, dt, g = _dw_check(form, geom, tuple(x_shape), w.shape, (dy,), w)
+    if tuple(dy.shape) != (g.N, g.P, g.Q, g.C * g.M):
+        raise Bad("depthwise conv: dy is %s, the geometry says %s" % (tuple(dy.shape), (g.N, g.P, g.Q, g.C * g.M)))
+    dx = _dw_out(out, (g.N, g.H, g.W, g.C), dy, "out")
+    _lib.call("ttdk_dwconv_dgrad", dy.data_ptr(), w.data_ptr(), dx.data_ptr(), dt, g, f, _s())
+    return dx
+
+
+def dwconv_wgrad_workspace(x_shape, w_shape, geom, device="cuda"):
+    """fp32 workspace for dwconv_wgrad: T partial rows (and one for the folded sum)."""
+    g = _plan.dw_geom(x_shape, w_shape, *DwGeom(*geom))
+    return torch.empty(_plan.dw_wgrad_ws_floats(g), dtype=torch.float32, device=device)
+
+
+def dwconv_wgrad(x, dy, w_shape, geom, out=None, accumulate=False, workspace=None, form="auto"):
+    """dw fp32 [R,S,C,M] (accumulate: added onto `out`) from x [N,H,W,C] and dy [N,P,Q,C*M].
+    Slab partials in `workspace` folded in a fixed order: the same bits on every run."""
+    from ..utils.errors import InvalidArgumentError as Bad
+    f, dt, g = _dw_check(form, geom, x.shape, tuple(w_shape), (x, dy))
+    if tuple(dy.shape) != (g.N, g.P, g.Q, g.C * g.M):
+        raise Bad("depthwise conv: dy is %s, the geometry says %s" % (tuple(dy.shape), (g.N, g.P, g.Q, g.C * g.M)))
+    if accumulate and out is None:
+        raise Bad("depthwise conv: accumulate=True needs out")
+    need = _plan.dw_wgrad_ws_floats(g)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=x.device)
+    if (workspace.dtype != torch.float32 or not workspace.is_cuda or not workspace.is_contiguous()
+            or workspace.numel() < need or workspace.data_ptr() % 16):
+        raise Bad("depthwise conv: workspace must be a 16-byte aligned contiguous float32 GPU tensor of >= %d "
+                  "elements" % need)
+    dw = _dw_out(out, tuple(w_shape), workspace, "out")
+    _lib.call("ttdk_dwconv_wgrad", x.data_ptr(), dy.data_ptr(), dw.data_ptr(), workspace.data_ptr(), need, dt, g,
+              int(bool(accumulate)), f, _s())
+    return dw
 
 
 def _ids(ids):
