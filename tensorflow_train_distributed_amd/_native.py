@@ -32,9 +32,10 @@ _OBJDIR = os.path.join(_LIBDIR, "obj")
 
 RT_LIB = os.path.join(_LIBDIR, "libttd_rt.so")
 # kernel-side headers the host runtime also compiles (the plans of the collective engine, the
-# direct xGMI all-reduce, the GEMM / convolution launchers and the depthwise convolution)
+# direct xGMI all-reduce, the GEMM / convolution launchers, the depthwise convolution and the
+# group normalisation)
 _RT_SHARED = [os.path.join(_CSRC, "kernels", h)
-              for h in ("collective_plan.h", "ipc_plan.h", "gemm_plan.h", "dwconv_plan.h")]
+              for h in ("collective_plan.h", "ipc_plan.h", "gemm_plan.h", "dwconv_plan.h", "groupnorm_plan.h")]
 HIP_LIB = os.path.join(_LIBDIR, "libttd_hip.so")
 
 HIP_ARCH = os.environ.get("TTD_HIP_ARCH", "gfx950")

@@ -384,6 +384,38 @@ class RMSNormalization(Layer):
         return N.rms_norm(x, self.gamma, self.epsilon)
 
 
+class GroupNormalization(Layer):
+    """Group normalisation over the last (channel) axis (Keras GroupNormalization(axis=-1)):
+    per-sample statistics over the spatial positions and the C / groups channels of a group; no
+    moving statistics, the same in training and inference. groups=-1: one group per channel
+    (instance normalisation). gamma / beta exist only with scale / center."""
+    _default_name = "group_normalization"
+
+    def __init__(self, groups=32, epsilon=1e-3, center=True, scale=True, name=None):
+        super().__init__(name)
+        self.groups, self.epsilon = int(groups), float(epsilon)
+        self.center, self.scale = bool(center), bool(scale)
+        if self.groups < 1 and self.groups != -1:
+            raise InvalidArgumentError("GroupNormalization: groups must be positive or -1, got %d" % self.groups)
+
+    def build(self, input_shape):
+        C = input_shape[-1]
+        G = C if self.groups == -1 else self.groups
+        if len(input_shape) < 2 or C < 1 or C % G:
+            raise InvalidArgumentError("GroupNormalization: %d groups do not divide the %s channels of input %s"
+                                       % (G, C, tuple(input_shape)))
+        self._G = G
+        if self.scale:
+            self.add_weight("gamma", (C,), "ones")
+        if self.center:
+            self.add_weight("beta", (C,), "zeros")
+        super().build(input_shape)
+
+    def call(self, x, **kw):
+        return N.group_norm(x, self.gamma if self.scale else None, self.beta if self.center else None, self._G,
+                            self.epsilon)
+
+
 class SwiGLU(Layer):
     """Gated SiLU unit: silu(x Wg + bg) * (x Wv + bv) as ONE fused projection, like `qkv/kernel`:
     kernel [in, 2*units] and bias [2*units] hold the gate columns first, then the value columns."""

@@ -24,6 +24,7 @@ accumulation) for either input dtype.
     ttd.nn.attention(q, k, v, 16, num_kv_heads=4)         # grouped-query: k, v [B, Sk, 4*64]
     ttd.nn.rotary_embedding(q, 16, offset=0)              # RoPE on q / k before attention
     ttd.nn.rms_norm(x, gamma); ttd.nn.swiglu(x)           # RMSNorm; silu(x[..., :I]) * x[..., I:]
+    ttd.nn.group_norm(x, gamma, beta, groups=32)          # [N, *spatial, C], per-sample group statistics
 """
 from __future__ import annotations
 
@@ -522,6 +523,72 @@ def rms_norm(x, gamma, eps: float = 1e-6):
         return _RMSNormGeneric.apply(x, gamma, float(eps))
     xf = x.float()
     y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gamma.float()
+    return y.to(x.dtype)
+
+
+class _GroupNorm(torch.autograd.Function):
+    """Any [N, *spatial, C], fp32 or bf16 (groupnorm.hip): slab partial sums folded in a fixed
+    order, per-(n, c) coefficient rows for the two apply kernels."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps):
+        from .ops import kernels as K
+        shp = x.shape
+        x3 = x.reshape(shp[0], -1, shp[-1]).contiguous()
+        g = _f32(gamma)
+        y, mean, rstd = K.group_norm_fwd(x3, g, _f32(beta), groups, eps)
+        ctx.save_for_backward(x3, g, mean, rstd)
+        ctx.cfg = (shp, None if gamma is None else gamma.dtype, None if beta is None else beta.dtype)
+        return y.reshape(shp)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import kernels as K
+        x3, g, mean, rstd = ctx.saved_tensors
+        shp, gdt, bdt = ctx.cfg
+        C = shp[-1]
+        need = ctx.needs_input_grad
+        dg = torch.empty(C, dtype=torch.float32, device=dy.device) if gdt is not None and need[1] else None
+        db = torch.empty(C, dtype=torch.float32, device=dy.device) if bdt is not None and need[2] else None
+        d3 = dy.reshape(x3.shape).contiguous().to(x3.dtype)
+        dx = K.group_norm_bwd(d3, x3, g, mean, rstd, dg, db, want_dx=need[0])
+        return ((dx.reshape(shp) if dx is not None else None), (dg.to(gdt) if dg is not None else None),
+                (db.to(bdt) if db is not None else None), None, None)
+
+
+def group_norm(x, gamma, beta, groups: int = 32, eps: float = 1e-3):
+    """Group normalisation over the last (channel) axis of x [N, *spatial, C] (Keras
+    GroupNormalization(axis=-1)): mean and biased variance over the spatial positions and the
+    C / groups consecutive channels of each group, per sample; y = (x - mean) * rsqrt(var + eps)
+    * gamma + beta with gamma / beta [C] or None. Statistics in fp32. GPU: groupnorm.hip, bf16
+    with C % 8 == 0 on the vectorised form, anything else (fp32 stays fp32) on the generic one.
+    CPU: the fp32 formula in torch ops."""
+    groups = int(groups)
+    if x.dim() < 2:
+        raise InvalidArgumentError("ttd.nn.group_norm: x must be [N, ..., C] of rank >= 2, got %s" % (tuple(x.shape),))
+    C = x.shape[-1]
+    if groups < 1 or C < 1 or C % groups:
+        raise InvalidArgumentError("ttd.nn.group_norm: groups = %d must be positive and divide the %d channels"
+                                   % (groups, C))
+    for name, v in (("gamma", gamma), ("beta", beta)):
+        if v is not None and (v.dim() != 1 or v.shape[0] != C):
+            raise InvalidArgumentError("ttd.nn.group_norm: %s must be [%d] for x %s, got %s"
+                                       % (name, C, tuple(x.shape), tuple(v.shape)))
+        if v is not None and v.device != x.device:
+            raise InvalidArgumentError("ttd.nn.group_norm: %s is on %s, x on %s" % (name, v.device, x.device))
+    if _on_gpu(x, gamma, beta):
+        if x.numel() == 0:
+            raise InvalidArgumentError("ttd.nn.group_norm: empty input %s" % (tuple(x.shape),))
+        return _GroupNorm.apply(x, gamma, beta, groups, float(eps))
+    shp = x.shape
+    xf = x.float().reshape(shp[0], -1, groups, C // groups)
+    mean = xf.mean((1, 3), keepdim=True)
+    var = (xf - mean).pow(2).mean((1, 3), keepdim=True)
+    y = ((xf - mean) * torch.rsqrt(var + eps)).reshape(shp)
+    if gamma is not None:
+        y = y * gamma.float()
+    if beta is not None:
+        y = y + beta.float()
     return y.to(x.dtype)
 
 

@@ -166,3 +166,88 @@ def dw_part_stride(g) -> int:
 
 def dw_wgrad_ws_floats(g) -> int:
     return _dw("wgrad_ws_floats")(ctypes.byref(g))
+
+
+# ------------------------------------------------------------------ group normalisation
+# csrc/kernels/groupnorm_plan.h, exported as ttd_gnplan_*; shapes are x [N, M, C] with G groups
+_GN_SIGS = {
+    "valid": (c_int, [c_longlong] * 4),
+    "fast_takes": (c_int, [c_longlong] * 4 + [c_int]),
+    "max_slabs": (c_int, []),
+    "max_ws_floats": (c_longlong, []),
+    "lanes": (c_int, [c_longlong, c_int]),
+    "rows_per_block": (c_int, [c_longlong, c_int]),
+    "part_stride": (c_longlong, [c_longlong]),
+    "rows_per_slab": (c_longlong, [c_longlong] * 3),
+    "parts": (c_int, [c_longlong] * 3),
+    "slab_rows": (None, [c_longlong] * 3 + [c_int, _PL, _PL]),
+    "fwd_ws_floats": (c_longlong, [c_longlong] * 3),
+    "bwd_ws_floats": (c_longlong, [c_longlong] * 3),
+}
+_gn_fns = {}
+
+
+def _gn(name):
+    if not _gn_fns:
+        lib = _native.rt()
+        for n, (res, args) in _GN_SIGS.items():
+            f = getattr(lib, "ttd_gnplan_" + n)
+            f.restype, f.argtypes = res, args
+            _gn_fns[n] = f
+    return _gn_fns[name]
+
+
+def gn_valid(N, M, C, G) -> bool:
+    return bool(_gn("valid")(N, M, C, G))
+
+
+def gn_fast_takes(N, M, C, G, bf16: bool) -> bool:
+    """Whether the fast form admits the shape, as far as shape and dtype decide (the launchers
+    also want 16-byte aligned bases)."""
+    return bool(_gn("fast_takes")(N, M, C, G, 1 if bf16 else 0))
+
+
+def gn_max_slabs() -> int:
+    return _gn("max_slabs")()
+
+
+def gn_max_ws_floats() -> int:
+    return _gn("max_ws_floats")()
+
+
+def gn_lanes(C, fast: bool) -> int:
+    """Lanes that share one pixel row in a streaming block."""
+    return _gn("lanes")(C, int(fast))
+
+
+def gn_rows_per_block(C, fast: bool) -> int:
+    """Pixel rows a streaming block has in flight."""
+    return _gn("rows_per_block")(C, int(fast))
+
+
+def gn_part_stride(C) -> int:
+    return _gn("part_stride")(C)
+
+
+def gn_rows_per_slab(N, M, C) -> int:
+    return _gn("rows_per_slab")(N, M, C)
+
+
+def gn_parts(N, M, C) -> int:
+    """Slabs T the M pixel rows of every image are cut into."""
+    return _gn("parts")(N, M, C)
+
+
+def gn_slab_rows(N, M, C, t):
+    """[r0, r1) of slab t of an image."""
+    r0, r1 = c_longlong(), c_longlong()
+    _gn("slab_rows")(N, M, C, t, r0, r1)
+    return r0.value, r1.value
+
+
+def gn_fwd_ws_floats(N, M, C) -> int:
+    return _gn("fwd_ws_floats")(N, M, C)
+
+
+def gn_bwd_ws_floats(N, M, C) -> int:
+    return _gn("bwd_ws_floats")(N, M, C)

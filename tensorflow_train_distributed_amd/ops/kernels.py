@@ -741,6 +741,126 @@ def dwconv_wgrad(x, dy, w_shape, geom, out=None, accumulate=False, workspace=Non
     return dw
 
 
+# ------------------------------------------------------------------ group normalisation (groupnorm.hip)
+_lib.register({
+    "ttdk_group_norm_fwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.L, _lib.L, _lib.I,
+                            _lib.I, _lib.F, _lib.I, _lib.I, _lib.P],
+    "ttdk_group_norm_bwd_stats": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.L,
+                                  _lib.L, _lib.I, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P],
+    "ttdk_group_norm_bwd_dx": [_lib.P, _lib.P, _lib.P, _lib.L, _lib.P, _lib.L, _lib.L, _lib.I, _lib.I, _lib.I, _lib.I,
+                               _lib.P],
+})
+
+_GN_FORMS = {"auto": 0, "generic": 1}
+
+
+def _gn_check(form, groups, acts, vectors=()):
+    """Argument checks shared by the group norm launchers: `acts` are [N, M, C] tensors of one
+    dtype, `vectors` (name, tensor or None) fp32 [C]. Returns (form code, dt, N, M, C, G)."""
+    from ..utils.errors import InvalidArgumentError as Bad
+    if form not in _GN_FORMS:
+        raise Bad("group norm: form must be 'auto' or 'generic', got %r" % (form,))
+    x = acts[0]
+    if x.dim() != 3:
+        raise Bad("group norm: tensors must be [N, M, C], got %s" % (tuple(x.shape),))
+    if x.dtype not in _DT:
+        raise Bad("group norm: activations must be float32 or bfloat16, got %s" % x.dtype)
+    for t in acts:
+        if t.dtype != x.dtype or tuple(t.shape) != tuple(x.shape):
+            raise Bad("group norm: activations of one dtype and shape per call, got %s %s and %s %s"
+                      % (x.dtype, tuple(x.shape), t.dtype, tuple(t.shape)))
+        if not t.is_cuda or not t.is_contiguous():
+            raise Bad("group norm: tensors must be contiguous and on the GPU")
+    N, M, C = (int(v) for v in x.shape)
+    G = int(groups)
+    if x.numel() == 0:
+        raise Bad("group norm: empty input %s" % (tuple(x.shape),))
+    if G < 1 or C % G:
+        raise Bad("group norm: groups = %d must be positive and divide the %d channels" % (G, C))
+    if not _plan.gn_valid(N, M, C, G):
+        raise Bad("group norm: shape %s with %d groups is out of range" % (tuple(x.shape), G))
+    for name, v in vectors:
+        if v is not None and (v.dtype != torch.float32 or not v.is_cuda or v.device != x.device
+                              or not v.is_contiguous() or tuple(v.shape) != (C,)):
+            raise Bad("group norm: %s must be a contiguous float32 tensor [%d] on the input's GPU" % (name, C))
+    return _GN_FORMS[form], _DT[x.dtype], N, M, C, G
+
+
+def _gn_stat(t, N, G, like, what):
+    from ..utils.errors import InvalidArgumentError as Bad
+    if (t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous() or tuple(t.shape) != (N, G)):
+        raise Bad("group norm: %s must be a contiguous float32 tensor [%d, %d] on the input's GPU" % (what, N, G))
+    return t
+
+
+def _gn_workspace(workspace, need, like):
+    from ..utils.errors import InvalidArgumentError as Bad
+    if workspace is None:
+        return torch.empty(need, dtype=torch.float32, device=like.device)
+    if (workspace.dtype != torch.float32 or workspace.device != like.device or not workspace.is_contiguous()
+            or workspace.numel() < need or workspace.data_ptr() % 16):
+        raise Bad("group norm: workspace must be a 16-byte aligned contiguous float32 GPU tensor of >= %d elements"
+                  % need)
+    return workspace
+
+
+def _gn_out(out, like):
+    from ..utils.errors import InvalidArgumentError as Bad
+    if out is None:
+        return torch.empty_like(like)
+    if (tuple(out.shape) != tuple(like.shape) or out.dtype != like.dtype or out.device != like.device
+            or not out.is_contiguous()):
+        raise Bad("group norm: out must be a contiguous %s GPU tensor of shape %s" % (like.dtype, tuple(like.shape)))
+    return out
+
+
+def group_norm_fwd_workspace(N, M, C, device="cuda"):
+    return torch.empty(_plan.gn_fwd_ws_floats(N, M, C), dtype=torch.float32, device=device)
+
+
+def group_norm_bwd_workspace(N, M, C, device="cuda"):
+    return torch.empty(_plan.gn_bwd_ws_floats(N, M, C), dtype=torch.float32, device=device)
+
+
+def group_norm_fwd(x3, gamma, beta, groups, eps, out=None, workspace=None, form="auto", stats=None):
+    """Group normalisation of x3 [N, M, C] (bf16 / fp32, channels last) in `groups` groups of
+    consecutive channels; gamma / beta fp32 [C] or None. Returns (y, mean [N, G], rstd [N, G]);
+    stats = (mean, rstd) supplies the two fp32 buffers. form 'generic' forces the scalar kernels."""
+    f, dt, N, M, C, G = _gn_check(form, groups, (x3,), (("gamma", gamma), ("beta", beta)))
+    y = _gn_out(out, x3)
+    if stats is None:
+        st = torch.empty((2, N, G), dtype=torch.float32, device=x3.device)
+        mean, rstd = st[0], st[1]
+    else:
+        mean, rstd = _gn_stat(stats[0], N, G, x3, "mean"), _gn_stat(stats[1], N, G, x3, "rstd")
+    need = _plan.gn_fwd_ws_floats(N, M, C)
+    ws = _gn_workspace(workspace, need, x3)
+    _lib.call("ttdk_group_norm_fwd", x3.data_ptr(), _p(gamma), _p(beta), y.data_ptr(), mean.data_ptr(),
+              rstd.data_ptr(), ws.data_ptr(), need, N, M, C, G, float(eps), dt, f, _s())
+    return y, mean, rstd
+
+
+def group_norm_bwd(dy3, x3, gamma, mean, rstd, dgamma, dbeta, want_dx=True, accumulate=False, out=None,
+                   workspace=None, form="auto"):
+    """Backward of group_norm_fwd from the saved x3, mean, rstd: writes dgamma / dbeta (fp32 [C],
+    either may be None; accumulate adds to their old contents) and returns dx, or None without
+    want_dx (no dx kernel is launched then). Partial rows folded in a fixed order: the same bits
+    on every run."""
+    G = mean.shape[-1] if mean.dim() == 2 else 0
+    f, dt, N, M, C, G = _gn_check(form, G, (dy3, x3), (("gamma", gamma), ("dgamma", dgamma), ("dbeta", dbeta)))
+    _gn_stat(mean, N, G, x3, "mean")
+    _gn_stat(rstd, N, G, x3, "rstd")
+    need = _plan.gn_bwd_ws_floats(N, M, C)
+    ws = _gn_workspace(workspace, need, x3)
+    dx = _gn_out(out, x3) if want_dx else None
+    _lib.call("ttdk_group_norm_bwd_stats", dy3.data_ptr(), x3.data_ptr(), _p(gamma), mean.data_ptr(), rstd.data_ptr(),
+              _p(dgamma), _p(dbeta), ws.data_ptr(), need, N, M, C, G, dt, int(bool(accumulate)), f, _s())
+    if want_dx:
+        _lib.call("ttdk_group_norm_bwd_dx", dy3.data_ptr(), x3.data_ptr(), ws.data_ptr(), need, dx.data_ptr(), N, M, C,
+                  G, dt, f, _s())
+    return dx
+
+
 def _ids(ids):
     if ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous():
         raise ValueError("ids must be a contiguous int32/int64 tensor")
