@@ -33,9 +33,9 @@ _OBJDIR = os.path.join(_LIBDIR, "obj")
 RT_LIB = os.path.join(_LIBDIR, "libttd_rt.so")
 # kernel-side headers the host runtime also compiles (the plans of the collective engine, the
 # direct xGMI all-reduce, the GEMM / convolution launchers, the depthwise convolution and the
-# group normalisation)
+# group normalisation; abi.h records the signatures of the exports Python calls)
 _RT_SHARED = [os.path.join(_CSRC, "kernels", h)
-              for h in ("collective_plan.h", "ipc_plan.h", "gemm_plan.h", "dwconv_plan.h", "groupnorm_plan.h")]
+              for h in ("collective_plan.h", "ipc_plan.h", "gemm_plan.h", "dwconv_plan.h", "groupnorm_plan.h", "abi.h")]
 HIP_LIB = os.path.join(_LIBDIR, "libttd_hip.so")
 
 HIP_ARCH = os.environ.get("TTD_HIP_ARCH", "gfx950")

@@ -1516,10 +1516,10 @@ using namespace ttdk;
 // causal != 0: query q attends keys k <= q (and k < seqlen[b]); needs Sq == Sk.
 // Grouped-query attention: k / v hold Hk heads (Hk * 64 columns), H % Hk == 0; query head h reads
 // key/value head h / (H / Hk). lse stays [B*H][Sq].
-TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+TTDK_API(int, ttdk_attn_fwd, (const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
                               long long ldv, bf16_t* o, long long ldo, float* lse, const int* seqlen, int B, int H,
                               int Hk, int Sq, int Sk, float p_drop, const long long* rng, unsigned site, int causal,
-                              hipStream_t st) {
+                              hipStream_t st)) {
   if (!args_ok(H, Hk, Sq, Sk, causal, p_drop, rng, ldq | ldk | ldv | ldo, {q, k, v, o})) return hipErrorInvalidValue;
   AttnParams P = make_params(B, H, Hk, Sq, Sk, seqlen, p_drop, rng, site);
   P.q = q; P.k = k; P.v = v; P.ldq = ldq; P.ldk = ldk; P.ldv = ldv;
@@ -1529,7 +1529,7 @@ TTDK_EXPORT int ttdk_attn_fwd(const bf16_t* q, long long ldq, const bf16_t* k, l
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_attn_set_fused_bwd(int on) {
+TTDK_API(int, ttdk_attn_set_fused_bwd, (int on)) {
   g_attn_fused = on ? 1 : 0;
   return 0;
 }
@@ -1542,11 +1542,11 @@ TTDK_EXPORT int ttdk_attn_set_fused_bwd(int on) {
 // H / Hk query heads in head order). The fused kernel, when switched on, takes only what it has a
 // form for: not causal, Sq == Sk, Hk == H, S in kFusedBwd; everything else runs the split kernels
 // whatever the switch says.
-TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+TTDK_API(int, ttdk_attn_bwd, (const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
                               long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
                               const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk, long long lddk,
                               bf16_t* dv, long long lddv, const int* seqlen, int B, int H, int Hk, int Sq, int Sk,
-                              float p_drop, const long long* rng, unsigned site, int causal, hipStream_t st) {
+                              float p_drop, const long long* rng, unsigned site, int causal, hipStream_t st)) {
   if (!args_ok(H, Hk, Sq, Sk, causal, p_drop, rng, ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv,
                {q, k, v, o, dout}))
     return hipErrorInvalidValue;
@@ -1584,8 +1584,8 @@ TTDK_EXPORT int ttdk_attn_bwd(const bf16_t* q, long long ldq, const bf16_t* k, l
 // window_left / window_right < 0: unbounded; causal clamps the right side to 0. One launch on st,
 // no allocation, no host synchronisation: it can be captured. Built once per step and shared by
 // every layer's forward and backward.
-TTDK_EXPORT int ttdk_attn_band(const int* segment_ids, const int* seqlen, int B, int S, int window_left,
-                               int window_right, int causal, int* table, hipStream_t st) {
+TTDK_API(int, ttdk_attn_band, (const int* segment_ids, const int* seqlen, int B, int S, int window_left,
+                               int window_right, int causal, int* table, hipStream_t st)) {
   if (B <= 0 || S <= 0 || S % QBLK || table == nullptr || (reinterpret_cast<uintptr_t>(table) & 15))
     return hipErrorInvalidValue;
   const int wl = window_left < 0 ? -1 : min(window_left, S);
@@ -1607,10 +1607,10 @@ bool band_params(AttnParams& P, const int* band, int B, int Sq, int Sk) {
 
 // ttdk_attn_fwd with the table of ttdk_attn_band in the place of seqlen and causal (both are in the
 // table). Self-attention only: Sq != Sk is refused.
-TTDK_EXPORT int ttdk_attn_band_fwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+TTDK_API(int, ttdk_attn_band_fwd, (const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
                                    long long ldv, bf16_t* o, long long ldo, float* lse, const int* band, int B, int H,
                                    int Hk, int Sq, int Sk, float p_drop, const long long* rng, unsigned site,
-                                   hipStream_t st) {
+                                   hipStream_t st)) {
   if (!args_ok(H, Hk, Sq, Sk, 1, p_drop, rng, ldq | ldk | ldv | ldo, {q, k, v, o})) return hipErrorInvalidValue;
   AttnParams P = make_params(B, H, Hk, Sq, Sk, nullptr, p_drop, rng, site);
   if (!band_params(P, band, B, Sq, Sk)) return hipErrorInvalidValue;
@@ -1622,11 +1622,11 @@ TTDK_EXPORT int ttdk_attn_band_fwd(const bf16_t* q, long long ldq, const bf16_t*
 
 // The backward of ttdk_attn_band_fwd: always the split kernels (the fused backward has no band
 // form), bwd_q then bwd_kv as in ttdk_attn_bwd.
-TTDK_EXPORT int ttdk_attn_band_bwd(const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
+TTDK_API(int, ttdk_attn_band_bwd, (const bf16_t* q, long long ldq, const bf16_t* k, long long ldk, const bf16_t* v,
                                    long long ldv, const bf16_t* o, long long ldo, const bf16_t* dout, long long lddo,
                                    const float* lse, float* delta, bf16_t* dq, long long lddq, bf16_t* dk,
                                    long long lddk, bf16_t* dv, long long lddv, const int* band, int B, int H, int Hk,
-                                   int Sq, int Sk, float p_drop, const long long* rng, unsigned site, hipStream_t st) {
+                                   int Sq, int Sk, float p_drop, const long long* rng, unsigned site, hipStream_t st)) {
   if (!args_ok(H, Hk, Sq, Sk, 1, p_drop, rng, ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv, {q, k, v, o, dout}))
     return hipErrorInvalidValue;
   const bool gqa = Hk != H, drop = p_drop > 0.f;

@@ -539,7 +539,7 @@ inline int grid_for(long long n, int per_block = kThreads, int cap = 8192) {
 using namespace ttdk;
 
 // Number of partial rows ttdk_bn_stats_partial / ttdk_bn_bwd_partial will write.
-TTDK_EXPORT int ttdk_bn_num_partials(long long M, int C) {
+TTDK_API(int, ttdk_bn_num_partials, (long long M, int C)) {
   const int cg = C >> 3;
   const int cols = cg < kThreads ? cg : kThreads;
   const int rlanes = kThreads / cols;
@@ -549,7 +549,7 @@ TTDK_EXPORT int ttdk_bn_num_partials(long long M, int C) {
   return static_cast<int>(want);
 }
 
-TTDK_EXPORT int ttdk_bn_stats_partial(const bf16_t* x, long long M, int C, float* partial, int nblocks, hipStream_t st) {
+TTDK_API(int, ttdk_bn_stats_partial, (const bf16_t* x, long long M, int C, float* partial, int nblocks, hipStream_t st)) {
   if (C % 8) return hipErrorInvalidValue;
   const long long rpb = (M + nblocks - 1) / nblocks;
   hipLaunchKernelGGL(stats_partial_kernel, dim3(nblocks), dim3(kThreads), 0, st, x, M, C, partial, rpb);
@@ -557,8 +557,8 @@ TTDK_EXPORT int ttdk_bn_stats_partial(const bf16_t* x, long long M, int C, float
 }
 
 // ReLU mask source: `mask` (1 bit per element, written by ttdk_bn_apply) if given, else `out`.
-TTDK_EXPORT int ttdk_bn_bwd_partial(const bf16_t* dy, const bf16_t* out, const uint8_t* mask, const bf16_t* y,
-                                    long long M, int C, float* partial, int nblocks, bf16_t* g_out, hipStream_t st) {
+TTDK_API(int, ttdk_bn_bwd_partial, (const bf16_t* dy, const bf16_t* out, const uint8_t* mask, const bf16_t* y,
+                                    long long M, int C, float* partial, int nblocks, bf16_t* g_out, hipStream_t st)) {
   if (C % 8) return hipErrorInvalidValue;
   const long long rpb = (M + nblocks - 1) / nblocks;
   hipLaunchKernelGGL(bwd_partial_kernel, dim3(nblocks), dim3(kThreads), 0, st, dy, out, mask, y, M, C, partial, rpb,
@@ -567,7 +567,7 @@ TTDK_EXPORT int ttdk_bn_bwd_partial(const bf16_t* dy, const bf16_t* out, const u
 }
 
 // sums[2C] = sum of partial[T][2C] (sums is zeroed here).
-TTDK_EXPORT int ttdk_bn_reduce_partials(const float* partial, int T, int C, float* sums, hipStream_t st) {
+TTDK_API(int, ttdk_bn_reduce_partials, (const float* partial, int T, int C, float* sums, hipStream_t st)) {
   const int C2 = 2 * C;
   hipError_t e = hipMemsetAsync(sums, 0, sizeof(float) * C2, st);
   if (e != hipSuccess) return e;
@@ -579,26 +579,26 @@ TTDK_EXPORT int ttdk_bn_reduce_partials(const float* partial, int T, int C, floa
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bn_fwd_finalize(const float* sums, float count, int C, const float* gamma, const float* beta,
+TTDK_API(int, ttdk_bn_fwd_finalize, (const float* sums, float count, int C, const float* gamma, const float* beta,
                                      float eps, float momentum, float* running_mean, float* running_var,
-                                     float* save_mean, float* save_rstd, float* scale, float* shift, hipStream_t st) {
+                                     float* save_mean, float* save_rstd, float* scale, float* shift, hipStream_t st)) {
   hipLaunchKernelGGL(fwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, count, C, gamma, beta, eps,
                      momentum, running_mean, running_var, save_mean, save_rstd, scale, shift);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bn_bwd_finalize(const float* sums, float count, int C, const float* gamma, const float* mean,
+TTDK_API(int, ttdk_bn_bwd_finalize, (const float* sums, float count, int C, const float* gamma, const float* mean,
                                      const float* rstd, float* dgamma, float* dbeta, float* coef, int accumulate,
-                                     hipStream_t st) {
+                                     hipStream_t st)) {
   hipLaunchKernelGGL(bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, count, C, gamma, mean, rstd,
                      dgamma, dbeta, coef, accumulate);
   return hipGetLastError();
 }
 
 // q8/q8_slot (optional): also write an fp8 e4m3 copy of `out` (delayed scaling, see fp8.hip).
-TTDK_EXPORT int ttdk_bn_apply(const bf16_t* y, const float* scale, const float* shift, const bf16_t* residual,
+TTDK_API(int, ttdk_bn_apply, (const bf16_t* y, const float* scale, const float* shift, const bf16_t* residual,
                               const float* rscale, const float* rshift, bf16_t* out, uint8_t* mask, uint8_t* q8,
-                              float* q8_slot, long long n, int C, int relu, hipStream_t st) {
+                              float* q8_slot, long long n, int C, int relu, hipStream_t st)) {
   if (C % 8 || n % 8 || (q8 && !q8_slot) || (rscale && (!residual || !rshift)) || (!out && !q8)) return hipErrorInvalidValue;
   const long long n8 = n / 8;
   const int grid = grid_for(n8, kThreads * kUnroll);
@@ -611,9 +611,9 @@ TTDK_EXPORT int ttdk_bn_apply(const bf16_t* y, const float* scale, const float* 
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bn_bwd_apply_q8(const bf16_t* dy, const bf16_t* out, const uint8_t* mask, const bf16_t* y,
+TTDK_API(int, ttdk_bn_bwd_apply_q8, (const bf16_t* dy, const bf16_t* out, const uint8_t* mask, const bf16_t* y,
                                      const float* coef, bf16_t* dz, uint8_t* q8, float* q8_slot, long long n, int C,
-                                     hipStream_t st) {
+                                     hipStream_t st)) {
   if (C % 8 || n % 8 || (q8 && !q8_slot) || (!dz && !q8)) return hipErrorInvalidValue;
   const long long n8 = n / 8;
   const int grid = grid_for(n8, kThreads * kUnroll);
@@ -626,25 +626,25 @@ TTDK_EXPORT int ttdk_bn_bwd_apply_q8(const bf16_t* dy, const bf16_t* out, const 
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bn_bwd_apply(const bf16_t* dy, const bf16_t* out, const uint8_t* mask, const bf16_t* y,
-                                  const float* coef, bf16_t* dz, long long n, int C, hipStream_t st) {
+TTDK_API(int, ttdk_bn_bwd_apply, (const bf16_t* dy, const bf16_t* out, const uint8_t* mask, const bf16_t* y,
+                                  const float* coef, bf16_t* dz, long long n, int C, hipStream_t st)) {
   return ttdk_bn_bwd_apply_q8(dy, out, mask, y, coef, dz, nullptr, nullptr, n, C, st);
 }
 
 // Slab rows (slices) ttdk_bn_reduce_finalize uses for T partial rows: the caller provides a
 // slab of slices*2*C floats.
-TTDK_EXPORT int ttdk_bn_finalize_slices(int T) {
+TTDK_API(int, ttdk_bn_finalize_slices, (int T)) {
   int s = (T + 31) / 32;
   return s < 1 ? 1 : (s > 256 ? 256 : s);
 }
 
 // bwd == 0: mean/rstd/scale/shift (+ running stats) from the fwd partials;
 // bwd == 1: dgamma/dbeta/coef from the bwd partials (mean/rstd inputs).
-TTDK_EXPORT int ttdk_bn_reduce_finalize(const float* partial, int T, int C, float* slab, int bwd, float count,
+TTDK_API(int, ttdk_bn_reduce_finalize, (const float* partial, int T, int C, float* slab, int bwd, float count,
                                         const float* gamma, const float* beta, float eps, float momentum,
                                         float* running_mean, float* running_var, float* mean, float* rstd,
                                         float* scale, float* shift, float* dgamma, float* dbeta, float* coef,
-                                        int accumulate, hipStream_t st) {
+                                        int accumulate, hipStream_t st)) {
   const int S = ttdk_bn_finalize_slices(T);
   const int per = (T + S - 1) / S;
   FinalizeArgs a{count, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd, scale, shift,

@@ -334,18 +334,18 @@ void watchdog(Engine* e) {
 
 using namespace ttdk;
 
-TTDK_EXPORT const char* ttdc_error(void* h) {
+TTDK_API(const char*, ttdc_error, (void* h)) {
   Engine* e = static_cast<Engine*>(h);
   return e ? e->err.c_str() : g_err.c_str();
 }
 
-TTDK_EXPORT int ttdc_version() {
+TTDK_API(int, ttdc_version, ()) {
   int v = 0;
   ncclGetVersion(&v);
   return v;
 }
 
-TTDK_EXPORT int ttdc_unique_id(char* out) {
+TTDK_API(int, ttdc_unique_id, (char* out)) {
   ncclUniqueId id;
   const ncclResult_t r = ncclGetUniqueId(&id);
   if (r != ncclSuccess) {
@@ -359,8 +359,8 @@ TTDK_EXPORT int ttdc_unique_id(char* out) {
 // Create the communicator for (rank, nranks) from rank 0's unique id on `device`, plus its
 // stream (priority `prio`: 0 = normal, < 0 = higher). min/max_ctas <= 0 keep RCCL's defaults.
 // Starts the watchdog thread. Returns nullptr on failure (ttdc_error(nullptr) says why).
-TTDK_EXPORT void* ttdc_create(const char* id_bytes, int nranks, int rank, int device, int prio, int min_ctas,
-                              int max_ctas, double timeout_s, int nonblocking) {
+TTDK_API(void*, ttdc_create, (const char* id_bytes, int nranks, int rank, int device, int prio, int min_ctas,
+                              int max_ctas, double timeout_s, int nonblocking)) {
   Engine* e = new Engine();
   e->rank = rank;
   e->nranks = nranks;
@@ -397,7 +397,7 @@ TTDK_EXPORT void* ttdc_create(const char* id_bytes, int nranks, int rank, int de
   return e;
 }
 
-TTDK_EXPORT void* ttdc_stream(void* h) { return static_cast<Engine*>(h)->cs; }
+TTDK_API(void*, ttdc_stream, (void* h)) { return static_cast<Engine*>(h)->cs; }
 
 namespace ttdk {
 namespace {
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void comm_emulate_kernel(uint4* buf, long long
 
 // Interference harness: queue one emulated bucket all-reduce (comm_emulate_kernel) of `us`
 // microseconds on `stream`.
-TTDK_EXPORT int ttdc_emulate_bucket(hipStream_t stream, int ctas, double us, void* buf, long long nbytes) {
+TTDK_API(int, ttdc_emulate_bucket, (hipStream_t stream, int ctas, double us, void* buf, long long nbytes)) {
   int dev = 0, rate_khz = 0;
   hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0)
@@ -482,7 +482,7 @@ TTDK_EXPORT int ttdc_emulate_bucket(hipStream_t stream, int ctas, double us, voi
 
 // Pre-size the bf16 staging buffer of compressed buckets for buckets of up to `count` fp32
 // elements (call once before any step is captured).
-TTDK_EXPORT int ttdc_reserve(void* h, long long count) {
+TTDK_API(int, ttdc_reserve, (void* h, long long count)) {
   Engine* e = static_cast<Engine*>(h);
   Call call(e);
   if (e->failed) return -1;
@@ -516,19 +516,19 @@ int bucket_launch(Engine* e, void* buf, long long count, int dtype, int op, int 
 }  // namespace
 }  // namespace ttdk
 
-TTDK_EXPORT int ttdc_bucket(void* h, void* buf, long long count, int dtype, int op, int algo, int compress,
-                            hipStream_t producer) {
+TTDK_API(int, ttdc_bucket, (void* h, void* buf, long long count, int dtype, int op, int algo, int compress,
+                            hipStream_t producer)) {
   return bucket_launch(static_cast<Engine*>(h), buf, count, dtype, op, algo, compress, true, producer);
 }
 
 // ttdc_bucket without the fork: the caller already ordered the communicator stream (an event
 // node pair of a segmented hipGraph capture, utils/graphs.py).
-TTDK_EXPORT int ttdc_bucket_nofork(void* h, void* buf, long long count, int dtype, int op, int algo, int compress) {
+TTDK_API(int, ttdc_bucket_nofork, (void* h, void* buf, long long count, int dtype, int op, int algo, int compress)) {
   return bucket_launch(static_cast<Engine*>(h), buf, count, dtype, op, algo, compress, false, nullptr);
 }
 
 // Timing mode on (resets the bucket count) or off.
-TTDK_EXPORT void ttdc_set_timing(void* h, int on) {
+TTDK_API(void, ttdc_set_timing, (void* h, int on)) {
   Engine* e = static_cast<Engine*>(h);
   e->timing = on != 0;
   e->n_timed = 0;
@@ -536,7 +536,7 @@ TTDK_EXPORT void ttdc_set_timing(void* h, int on) {
 
 // After ttdc_synchronize: *busy_ms = sum over the timed buckets of their reduction time,
 // *span_ms = first bucket start -> last bucket end; returns the number of timed buckets.
-TTDK_EXPORT int ttdc_timing(void* h, float* busy_ms, float* span_ms) {
+TTDK_API(int, ttdc_timing, (void* h, float* busy_ms, float* span_ms)) {
   Engine* e = static_cast<Engine*>(h);
   *busy_ms = *span_ms = 0.f;
   for (int i = 0; i < e->n_timed; ++i) {
@@ -575,7 +575,7 @@ void arm(Engine* e, hipStream_t s) {
 }  // namespace
 }  // namespace ttdk
 
-TTDK_EXPORT int ttdc_join(void* h, hipStream_t consumer) {
+TTDK_API(int, ttdc_join, (void* h, hipStream_t consumer)) {
   Engine* e = static_cast<Engine*>(h);
   Call call(e);
   ncclComm_t c = e->comm.load();
@@ -593,7 +593,7 @@ TTDK_EXPORT int ttdc_join(void* h, hipStream_t consumer) {
 // Arm the watchdog after a hipGraph replay: a captured join records no marker (a captured
 // record never completes on its own), so the replaying thread calls this with the replay stream
 // once per replay and a step whose collectives never finish still trips the deadline.
-TTDK_EXPORT int ttdc_arm(void* h, hipStream_t s) {
+TTDK_API(int, ttdc_arm, (void* h, hipStream_t s)) {
   Engine* e = static_cast<Engine*>(h);
   if (e->failed || !e->comm.load()) return -1;
   if (capturing(s)) return set_err(e, "ttdc_arm: stream is capturing"), -1;
@@ -603,8 +603,8 @@ TTDK_EXPORT int ttdc_arm(void* h, hipStream_t s) {
 
 // Collective directly on stream `s` (metrics, SyncOnRead means, broadcasts of initial state).
 // kind 0: reduce (op, algo 0); 1: broadcast from `root`.
-TTDK_EXPORT int ttdc_collective(void* h, int kind, void* buf, long long count, int dtype, int op, int root,
-                                hipStream_t s) {
+TTDK_API(int, ttdc_collective, (void* h, int kind, void* buf, long long count, int dtype, int op, int root,
+                                hipStream_t s)) {
   Engine* e = static_cast<Engine*>(h);
   Call call(e);
   ncclComm_t c = e->comm.load();
@@ -617,7 +617,7 @@ TTDK_EXPORT int ttdc_collective(void* h, int kind, void* buf, long long count, i
 
 // Block the host until the communicator stream drained, polling for communicator errors
 // against the engine's deadline (a hung peer becomes an error instead of a hang).
-TTDK_EXPORT int ttdc_synchronize(void* h) {
+TTDK_API(int, ttdc_synchronize, (void* h)) {
   Engine* e = static_cast<Engine*>(h);
   hipEvent_t done = nullptr;
   std::vector<void*> retired;
@@ -676,11 +676,11 @@ TTDK_EXPORT int ttdc_synchronize(void* h) {
 }
 
 // Number of times the watchdog / a deadline aborted this communicator (0 or 1).
-TTDK_EXPORT int ttdc_aborts(void* h) { return static_cast<Engine*>(h)->aborts.load(); }
+TTDK_API(int, ttdc_aborts, (void* h)) { return static_cast<Engine*>(h)->aborts.load(); }
 
 // Fault injection (tests): queue a kernel on the communicator stream that holds it until
 // *flag (device-visible host memory) becomes non-zero or max_ms passed.
-TTDK_EXPORT int ttdc_debug_stall(void* h, const int* flag, int max_ms) {
+TTDK_API(int, ttdc_debug_stall, (void* h, const int* flag, int max_ms)) {
   Engine* e = static_cast<Engine*>(h);
   int rate_khz = 0;
   if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, e->device) != hipSuccess || rate_khz <= 0)
@@ -693,7 +693,7 @@ TTDK_EXPORT int ttdc_debug_stall(void* h, const int* flag, int max_ms) {
 
 // Bus bandwidth probe: `iters` all-reduces of buf[0:count) (fp32) on the communicator stream,
 // timed with HIP events. *ms = mean time per all-reduce.
-TTDK_EXPORT int ttdc_probe(void* h, void* buf, long long count, int iters, float* ms) {
+TTDK_API(int, ttdc_probe, (void* h, void* buf, long long count, int iters, float* ms)) {
   Engine* e = static_cast<Engine*>(h);
   if (e->failed || iters <= 0) return -1;
   hipEvent_t a, b;
@@ -726,7 +726,7 @@ TTDK_EXPORT int ttdc_probe(void* h, void* buf, long long count, int iters, float
 }
 
 // Abort (a failed peer: frees the communicator without waiting for the others) or destroy.
-TTDK_EXPORT void ttdc_destroy(void* h, int abort) {
+TTDK_API(void, ttdc_destroy, (void* h, int abort)) {
   Engine* e = static_cast<Engine*>(h);
   if (!e) return;
   {

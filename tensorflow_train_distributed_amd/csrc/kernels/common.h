@@ -3,14 +3,15 @@
 // Conventions used by every kernel file:
 //  * wave = 64 lanes; block sizes are multiples of 64;
 //  * activations are NHWC (channels-last) bf16; parameters/optimizer state fp32;
-//  * every exported launcher is `extern "C" int ttdk_*(..., hipStream_t)` and returns the
+//  * every exported launcher is `TTDK_API(int, ttdk_*, (..., hipStream_t))` (abi.h: extern "C",
+//    and its signature goes into the table Python types its calls from) and returns the
 //    hipError_t of the launch, so PyTorch's current stream (and hipGraph capture) drives it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define TTDK_EXPORT extern "C" __attribute__((visibility("default")))
+#include "abi.h"
 
 typedef uint16_t bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;

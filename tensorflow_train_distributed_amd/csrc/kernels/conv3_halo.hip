@@ -801,7 +801,7 @@ int& conv3_feed_flag() {
 
 // Runtime switch of the prefetched feeding-BN epilogue of the halo data gradients (stream_epi.h:
 // feed_batch_*; 0 = the generic row loop); returns the previous setting. Results are bit-identical.
-TTDK_EXPORT int ttdk_set_conv3_feed(int on) {
+TTDK_API(int, ttdk_set_conv3_feed, (int on)) {
   const int old = conv3_feed_flag();
   conv3_feed_flag() = on ? 1 : 0;
   return old;
@@ -809,20 +809,20 @@ TTDK_EXPORT int ttdk_set_conv3_feed(int on) {
 
 // Runtime switch between the two schedules of both halo kernels (template parameter SCHED);
 // returns the previous setting. Results are bit-identical under both.
-TTDK_EXPORT int ttdk_set_conv3_sched(int on) {
+TTDK_API(int, ttdk_set_conv3_sched, (int on)) {
   const int old = conv3_sched_flag();
   conv3_sched_flag() = on ? 1 : 0;
   return old;
 }
 
 // Runtime switch of the stage-3 streamed-filter variant; returns the previous setting.
-TTDK_EXPORT int ttdk_set_conv3_s3(int on) {
+TTDK_API(int, ttdk_set_conv3_s3, (int on)) {
   const int old = conv3_s3_flag();
   conv3_s3_flag() = on;
   return old;
 }
 
-TTDK_EXPORT int ttdk_conv3_rows(int H, int W, int C, int N, int pro) {
+TTDK_API(int, ttdk_conv3_rows, (int H, int W, int C, int N, int pro)) {
   if (conv3_s3_flag() && c3s::fits(H, W, C, N, pro)) return 8 * W;  // tiles of 8 rows of the flattened (image, row) sequence
   const int th = c3::pick_th(C, N, W, pro);
   return (th && H % th == 0) ? th * W : 0;
@@ -832,9 +832,9 @@ TTDK_EXPORT int ttdk_conv3_rows(int H, int W, int C, int N, int pro) {
 //   pro 0: x; pro 1: relu(x*s + b); pro 2: s[0]*(x . mask) + s[1]*x2 + s[2] (s = coef[3][C]).
 // flip = 0: w is the forward filter [N][3][3][C]; flip = 1: w is the transposed filter
 // [N][3][3][C] of the conv whose data gradient this is (taps reversed here).
-TTDK_EXPORT int ttdk_conv3_halo(const bf16_t* x, const bf16_t* x2, const uint8_t* mask_in, const float* s,
+TTDK_API(int, ttdk_conv3_halo, (const bf16_t* x, const bf16_t* x2, const uint8_t* mask_in, const float* s,
                                 const float* b, bf16_t* side, uint8_t* side_mask, int pro, int flip, const bf16_t* w,
-                                int Nimg, int H, int W, int C, int N, const TtdkEpilogue* epi, hipStream_t st) {
+                                int Nimg, int H, int W, int C, int N, const TtdkEpilogue* epi, hipStream_t st)) {
   const int sched = conv3_sched_flag();
   if (ttdk_conv3_rows(H, W, C, N, pro) == 8 * W && c3s::fits(H, W, C, N, pro)) {
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return hipErrorInvalidValue;

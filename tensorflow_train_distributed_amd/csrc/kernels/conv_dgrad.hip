@@ -5,8 +5,8 @@
 // (ttdk_conv_weight_transpose). Rows of the GEMM are the pixels of dx.
 // Strided 1x1 (no padding) convs compute only the rows that receive a gradient and use the
 // epilogue's row remap; the caller zero-fills or pre-loads (beta=1) the other pixels.
-TTDK_EXPORT int ttdk_conv_dgrad(const bf16_t* dy, const bf16_t* wt, const TtdkConv* g, int bm, int bn,
-                                const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_conv_dgrad, (const bf16_t* dy, const bf16_t* wt, const TtdkConv* g, int bm, int bn,
+                                const TtdkEpilogue* epi, hipStream_t st)) {
   if (g->K % 8) return hipErrorInvalidValue;
   EpiParams pe = to_epi(epi);
   if (pe.by && (pe.stat == nullptr || pe.mode != 0 || g->C % 8 || pe.ldo % 8 || pe.residual || pe.act))
@@ -71,8 +71,8 @@ TTDK_EXPORT int ttdk_conv_dgrad(const bf16_t* dy, const bf16_t* wt, const TtdkCo
 //   dx = dz . W  (+ the usual epilogue: accumulate, feeding-BN statistics)
 // dz is also stored (by the workgroups of tile column 0) for the weight gradient. Returns
 // hipErrorNotSupported when the shape is not on the 256-row kernel (the caller keeps the pass).
-TTDK_EXPORT int ttdk_conv_dgrad_bnpro(const bf16_t* g_in, const bf16_t* wt, const TtdkConv* g, const bf16_t* y,
-                                      const float* coef, bf16_t* dz, const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_conv_dgrad_bnpro, (const bf16_t* g_in, const bf16_t* wt, const TtdkConv* g, const bf16_t* y,
+                                      const float* coef, bf16_t* dz, const TtdkEpilogue* epi, hipStream_t st)) {
   if (!plan::conv_dgrad_bnpro_takes(*g)) return hipErrorNotSupported;
   EpiParams pe = to_epi(epi);
   if (pe.by && (pe.stat == nullptr || pe.mode != 0 || g->C % 8 || pe.ldo % 8 || pe.residual || pe.act))
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(256) void subpixel_weights_kernel(const bf16_t* __r
 // scratch for the phase sub-kernels, C*R*S*Kout bf16 (the size of wt); ws_ready != 0: ws
 // already holds the phase filters in this launcher's phase order (ttdk_wprep, once per step),
 // wt is not read.
-TTDK_EXPORT int ttdk_conv_dgrad_subpixel(const bf16_t* dy, const bf16_t* wt, const TtdkConv* g, bf16_t* ws,
-                                         int ws_ready, const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_conv_dgrad_subpixel, (const bf16_t* dy, const bf16_t* wt, const TtdkConv* g, bf16_t* ws,
+                                         int ws_ready, const TtdkEpilogue* epi, hipStream_t st)) {
   const int s = g->sh;
   if (g->sw != s || s < 2 || g->dh != 1 || g->dw != 1 || g->R < s || g->S < s || g->K % 8 || g->C % 8)
     return hipErrorInvalidValue;

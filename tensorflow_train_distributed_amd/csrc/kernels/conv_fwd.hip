@@ -3,8 +3,8 @@
 
 // bm == 256 requests the LDS-DMA kernel (bn = its tile width 256 or 128; the caller sized
 // `stat` for 256-row tiles); the request fails loudly when the conv is not eligible.
-TTDK_EXPORT int ttdk_conv_fwd(const bf16_t* x, const bf16_t* w, const TtdkConv* g, int bm, int bn,
-                              const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_conv_fwd, (const bf16_t* x, const bf16_t* w, const TtdkConv* g, int bm, int bn,
+                              const TtdkEpilogue* epi, hipStream_t st)) {
   if (g->C % 8) return hipErrorInvalidValue;
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->P * g->Q, N = g->K, K = g->R * g->S * g->C;
@@ -35,9 +35,9 @@ TTDK_EXPORT int ttdk_conv_fwd(const bf16_t* x, const bf16_t* w, const TtdkConv* 
 // and stores h + its ReLU bits (tile column 0) — the unit's BN apply pass disappears.
 // coef = [sc | sh (| rsc | rsh)] fp32 [2 or 4][C]. hipErrorNotSupported when the shape is not on
 // the 256-row kernel (the caller keeps the pass). `stat` rows are 256-row tiles.
-TTDK_EXPORT int ttdk_conv_fwd_bnpro(const bf16_t* y3, const bf16_t* w, const TtdkConv* g, const bf16_t* res,
+TTDK_API(int, ttdk_conv_fwd_bnpro, (const bf16_t* y3, const bf16_t* w, const TtdkConv* g, const bf16_t* res,
                                     const float* coef, int proj, bf16_t* h_out, uint8_t* mask_out,
-                                    const TtdkEpilogue* epi, hipStream_t st) {
+                                    const TtdkEpilogue* epi, hipStream_t st)) {
   if (!plan::conv_fwd_bnpro_takes(*g) || !res || !h_out || !mask_out) return hipErrorNotSupported;
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->P * g->Q, N = g->K, K = g->C;
@@ -61,8 +61,8 @@ TTDK_EXPORT int ttdk_conv_fwd_bnpro(const bf16_t* y3, const bf16_t* w, const Ttd
 
 // fp8 forward conv / GEMM on the block-scaled MFMA: x8 [N,H,W,C] and w8 [K][R][S][C] in fp8
 // e4m3 (per-tensor scales folded into epi->alpha by the caller). C % 128 == 0, 256-row tiles.
-TTDK_EXPORT int ttdk_conv_fwd_fp8(const uint8_t* x8, const uint8_t* w8, const TtdkConv* g, int bn,
-                                  const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_conv_fwd_fp8, (const uint8_t* x8, const uint8_t* w8, const TtdkConv* g, int bn,
+                                  const TtdkEpilogue* epi, hipStream_t st)) {
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->P * g->Q, N = g->K, K = g->R * g->S * g->C;
   const int bbn = N >= 256 ? 256 : 128;  // fp8 always runs the LDS-DMA kernel (edges are clamped)
@@ -80,8 +80,8 @@ TTDK_EXPORT int ttdk_conv_fwd_fp8(const uint8_t* x8, const uint8_t* w8, const Tt
 
 // fp8 GEMM C[M,N] = A[M,K] . B[N,K]^T (both K-major fp8; a_fmt 0 = e4m3, 1 = e5m2; B e4m3),
 // K % 128 == 0, fused bf16 epilogue or fp32 (split-K slab) output like ttdk_gemm_bf16.
-TTDK_EXPORT int ttdk_gemm_fp8(const uint8_t* A, long long lda, const uint8_t* B, long long ldb, int a_fmt, int M,
-                              int N, int K, int splits, const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_gemm_fp8, (const uint8_t* A, long long lda, const uint8_t* B, long long ldb, int a_fmt, int M,
+                              int N, int K, int splits, const TtdkEpilogue* epi, hipStream_t st)) {
   EpiParams pe = to_epi(epi);
   const int bbn = N >= 256 ? 256 : 128;  // fp8 always runs the LDS-DMA kernel (edges are clamped)
   if (M < 1 || N < 1 || K % 128 || lda % 16 || ldb % 16 || pe.remap) return hipErrorInvalidValue;
@@ -102,8 +102,8 @@ TTDK_EXPORT int ttdk_gemm_fp8(const uint8_t* A, long long lda, const uint8_t* B,
 // epi.ascale1) of the implicit-GEMM gather, with the bf16 path's epilogues (accumulate, next BN's
 // masked gradient + backward statistics on 256-row tiles). K % 128 == 0 (one 128-element K-tile
 // inside one tap).
-TTDK_EXPORT int ttdk_conv_dgrad_fp8(const uint8_t* dy8, const uint8_t* wt8, const TtdkConv* g, const TtdkEpilogue* epi,
-                                    hipStream_t st) {
+TTDK_API(int, ttdk_conv_dgrad_fp8, (const uint8_t* dy8, const uint8_t* wt8, const TtdkConv* g, const TtdkEpilogue* epi,
+                                    hipStream_t st)) {
   if (g->sh != 1 || g->sw != 1 || g->dh != 1 || g->dw != 1 || g->K % 128 || g->C % 8) return hipErrorInvalidValue;
   EpiParams pe = to_epi(epi);
   if (pe.remap || pe.residual || pe.bH || pe.by2 || pe.mode != 0) return hipErrorInvalidValue;

@@ -25,8 +25,8 @@ static EpiParams wgrad_epi(int M, int N, int splits, float* dw, float* ws, int b
 
 // dw[K,R,S,C] (fp32) = sum over pixels of dy ⊗ im2col(x). `ws` is a split-K workspace of
 // splits*K*R*S*C floats (may be null when splits == 1, then dw is written directly).
-TTDK_EXPORT int ttdk_conv_wgrad(const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
-                                int splits, int beta, int bm, int bn, hipStream_t st) {
+TTDK_API(int, ttdk_conv_wgrad, (const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
+                                int splits, int beta, int bm, int bn, hipStream_t st)) {
   const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
   if (g->C % 8 || g->K % 8) return hipErrorInvalidValue;
   const int bbn = (bm == 0 || bm == 256) ? big_bn_wgrad(M, N, K) : 0;
@@ -78,9 +78,9 @@ TTDK_EXPORT int ttdk_conv_wgrad(const bf16_t* x, const bf16_t* dy, const TtdkCon
 // dy = coef[0]*g + coef[1]*y + coef[2] per output channel (see MNDenseBN). Only the 4-wave
 // im2col-gather path (non-pointwise convs too small for the 256-row kernel, e.g. the stem);
 // returns hipErrorInvalidValue where ttdk_conv_wgrad would pick another kernel.
-TTDK_EXPORT int ttdk_conv_wgrad_bn(const bf16_t* x, const bf16_t* g, const bf16_t* y, const float* coef,
+TTDK_API(int, ttdk_conv_wgrad_bn, (const bf16_t* x, const bf16_t* g, const bf16_t* y, const float* coef,
                                    const TtdkConv* gm, float* dw, float* ws, int splits, int beta, int bm, int bn,
-                                   hipStream_t st) {
+                                   hipStream_t st)) {
   const int M = gm->K, N = gm->R * gm->S * gm->C, K = gm->N * gm->P * gm->Q;
   if (!plan::conv_wgrad_bn_takes(*gm)) return hipErrorInvalidValue;
   if (bm == 0 || bn == 0 || bm == 256) pick_tile(M, N, &bm, &bn);
@@ -101,9 +101,9 @@ TTDK_EXPORT int ttdk_conv_wgrad_bn(const bf16_t* x, const bf16_t* g, const bf16_
 // block-scaled fp8 MFMA at twice the bf16 rate; ascale_dy / ascale_x: the inverse quantisation
 // scales (device fp32), folded into the fp32 output. Requires C, K % 16 == 0, pixels % 128 == 0,
 // 9C >= 256 (K < 256 output channels leave part of the 256-row tile idle).
-TTDK_EXPORT int ttdk_conv_wgrad_fp8(const uint8_t* x8, const uint8_t* dy8, const TtdkConv* g, float* dw, float* ws,
+TTDK_API(int, ttdk_conv_wgrad_fp8, (const uint8_t* x8, const uint8_t* dy8, const TtdkConv* g, float* dw, float* ws,
                                     int splits, int beta, const float* ascale_dy, const float* ascale_x,
-                                    hipStream_t st) {
+                                    hipStream_t st)) {
   const int M = g->K, N = g->R * g->S * g->C, K = g->N * g->P * g->Q;
   if (!plan::conv_wgrad_fp8_takes(*g) || !ascale_dy || !ascale_x || (reinterpret_cast<uintptr_t>(x8) & 15) ||
       (reinterpret_cast<uintptr_t>(dy8) & 15))

@@ -47,7 +47,7 @@
 #include "dwconv_plan.h"
 
 // transformer.hip
-TTDK_EXPORT int ttdk_colreduce(const float* part, int nb, int C, int stride, float* out, int beta, hipStream_t st);
+extern "C" int ttdk_colreduce(const float* part, int nb, int C, int stride, float* out, int beta, hipStream_t st);
 
 namespace ttdk {
 namespace {
@@ -508,14 +508,14 @@ void generic_wgrad(const void* x, const void* dy, float* part, const TtdkDwConv&
 using namespace ttdk;
 
 // Slabs T of the weight gradient and its workspace in floats ((T + 1) padded partial rows).
-TTDK_EXPORT int ttdk_dwconv_wgrad_parts(const TtdkDwConv* g) { return dwplan::valid(*g) ? dwplan::wgrad_parts(*g) : 0; }
-TTDK_EXPORT long long ttdk_dwconv_wgrad_ws_floats(const TtdkDwConv* g) {
+TTDK_API(int, ttdk_dwconv_wgrad_parts, (const TtdkDwConv* g)) { return dwplan::valid(*g) ? dwplan::wgrad_parts(*g) : 0; }
+TTDK_API(long long, ttdk_dwconv_wgrad_ws_floats, (const TtdkDwConv* g)) {
   return dwplan::valid(*g) ? dwplan::wgrad_ws_floats(*g) : 0;
 }
 
 // y [N,P,Q,C*M] = dwconv(x [N,H,W,C], w fp32 [R,S,C,M]); x, y of type dt.
-TTDK_EXPORT int ttdk_dwconv_fwd(const void* x, const float* w, void* y, int dt, const TtdkDwConv* gp, int form,
-                                hipStream_t st) {
+TTDK_API(int, ttdk_dwconv_fwd, (const void* x, const float* w, void* y, int dt, const TtdkDwConv* gp, int form,
+                                hipStream_t st)) {
   const TtdkDwConv g = *gp;
   if (!dwplan::valid(g) || !x || !w || !y || (dt != 0 && dt != 1)) return hipErrorInvalidValue;
   if (form == 0 && dwplan::fast_takes(g, dt) && aligned16(x) && aligned16(w) && aligned16(y)) {
@@ -536,8 +536,8 @@ TTDK_EXPORT int ttdk_dwconv_fwd(const void* x, const float* w, void* y, int dt, 
 }
 
 // dx [N,H,W,C] from dy [N,P,Q,C*M]; every element of dx is written.
-TTDK_EXPORT int ttdk_dwconv_dgrad(const void* dy, const float* w, void* dx, int dt, const TtdkDwConv* gp, int form,
-                                  hipStream_t st) {
+TTDK_API(int, ttdk_dwconv_dgrad, (const void* dy, const float* w, void* dx, int dt, const TtdkDwConv* gp, int form,
+                                  hipStream_t st)) {
   const TtdkDwConv g = *gp;
   if (!dwplan::valid(g) || !dy || !w || !dx || (dt != 0 && dt != 1)) return hipErrorInvalidValue;
   if (form == 0 && dwplan::fast_takes(g, dt) && aligned16(dy) && aligned16(w) && aligned16(dx)) {
@@ -561,8 +561,8 @@ TTDK_EXPORT int ttdk_dwconv_dgrad(const void* dy, const float* w, void* dx, int 
 
 // dw fp32 [R,S,C,M] = (beta ? dw : 0) + the weight gradient of x [N,H,W,C], dy [N,P,Q,C*M] (type
 // dt). ws: 16-byte aligned fp32 workspace of at least ttdk_dwconv_wgrad_ws_floats(g) floats.
-TTDK_EXPORT int ttdk_dwconv_wgrad(const void* x, const void* dy, float* dw, float* ws, long long ws_floats, int dt,
-                                  const TtdkDwConv* gp, int beta, int form, hipStream_t st) {
+TTDK_API(int, ttdk_dwconv_wgrad, (const void* x, const void* dy, float* dw, float* ws, long long ws_floats, int dt,
+                                  const TtdkDwConv* gp, int beta, int form, hipStream_t st)) {
   const TtdkDwConv g = *gp;
   if (!dwplan::valid(g) || !x || !dy || !dw || !ws || (dt != 0 && dt != 1)) return hipErrorInvalidValue;
   if (!aligned16(ws) || ws_floats < dwplan::wgrad_ws_floats(g)) return hipErrorInvalidValue;

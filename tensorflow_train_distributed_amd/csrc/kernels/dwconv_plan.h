@@ -6,6 +6,8 @@
 // functions (runtime/dwconv_plan.cc) to ops/_plan.py, and tests/test_depthwise_cpu.py pins them
 // without a GPU. Pointer alignment is checked by the launchers.
 
+#include "abi.h"
+
 // Geometry passed from Python (ops/_lib.py DwConvGeom, identical layout): input NHWC [N,H,W,C],
 // filter fp32 [R,S,C,M], output [N,P,Q,C*M]; output channel c*M+m reads input channel c.
 struct TtdkDwConv {
@@ -13,6 +15,10 @@ struct TtdkDwConv {
   int M, R, S;
   int P, Q;
   int sh, sw, ph, pw, dh, dw;
+};
+template <>
+struct ttd_abi::Code<const TtdkDwConv*> {
+  static constexpr char code = 'D';
 };
 
 namespace ttdk {

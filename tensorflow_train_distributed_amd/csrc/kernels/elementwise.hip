@@ -458,25 +458,25 @@ __global__ void dequant_fp8_kernel(const uint8_t* __restrict__ q, bf16_t* __rest
 
 using namespace ttdk;
 
-TTDK_EXPORT int ttdk_f32_to_bf16(const float* x, bf16_t* y, long long n, hipStream_t st) {
+TTDK_API(int, ttdk_f32_to_bf16, (const float* x, bf16_t* y, long long n, hipStream_t st)) {
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, x, y, n);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bf16_round_probe(const float* x, bf16_t* one, uint32_t* pair, void* eight, long long n,
-                                      hipStream_t st) {
+TTDK_API(int, ttdk_bf16_round_probe, (const float* x, bf16_t* one, uint32_t* pair, void* eight, long long n,
+                                      hipStream_t st)) {
   if (n % 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bf16_round_probe_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, x, one, pair,
                      static_cast<uint4*>(eight), n / 8);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bf16_to_f32(const bf16_t* x, float* y, long long n, hipStream_t st) {
+TTDK_API(int, ttdk_bf16_to_f32, (const bf16_t* x, float* y, long long n, hipStream_t st)) {
   hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, n);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_pad_channels(const bf16_t* x, bf16_t* y, long long rows, int C, int Cp, hipStream_t st) {
+TTDK_API(int, ttdk_pad_channels, (const bf16_t* x, bf16_t* y, long long rows, int C, int Cp, hipStream_t st)) {
   if (C == 3 && Cp == 8 && rows % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
     hipLaunchKernelGGL(pad3to8_kernel, dim3(grid_for(rows / 8)), dim3(256), 0, st, x, y, rows / 8);
@@ -486,21 +486,21 @@ TTDK_EXPORT int ttdk_pad_channels(const bf16_t* x, bf16_t* y, long long rows, in
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_unpad_channels(const bf16_t* x, bf16_t* y, long long rows, int Cp, int C, hipStream_t st) {
+TTDK_API(int, ttdk_unpad_channels, (const bf16_t* x, bf16_t* y, long long rows, int Cp, int C, hipStream_t st)) {
   hipLaunchKernelGGL(unpad_channels_kernel, dim3(grid_for(rows * C)), dim3(256), 0, st, x, y, rows, Cp, C);
   return hipGetLastError();
 }
 
 // tab: n TransposeEntry rows (device memory, 32 B each; src / dst 16-B aligned, A and C
 // multiples of 128, tile_begin the running sum of (A/128)*(C/128)); tiles: the total
-TTDK_EXPORT int ttdk_transpose128_batch_bf16(const void* tab, int n, int tiles, hipStream_t st) {
+TTDK_API(int, ttdk_transpose128_batch_bf16, (const void* tab, int n, int tiles, hipStream_t st)) {
   if (n <= 0 || tiles <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(transpose128_batch_kernel, dim3(tiles), dim3(256), 0, st, static_cast<const TransposeEntry*>(tab), n);
   return hipGetLastError();
 }
 
 // [A][B][C] -> [C][B][A] bf16
-TTDK_EXPORT int ttdk_transpose_aca_bf16(const bf16_t* src, bf16_t* dst, int A, int B, int C, hipStream_t st) {
+TTDK_API(int, ttdk_transpose_aca_bf16, (const bf16_t* src, bf16_t* dst, int A, int B, int C, hipStream_t st)) {
   if (B == 1 && A % 128 == 0 && C % 128 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
     hipLaunchKernelGGL(transpose128_bf16_kernel, dim3((A / 128) * (C / 128)), dim3(256), 0, st,
@@ -560,22 +560,22 @@ __global__ __launch_bounds__(256) void wprep_kernel(const bf16_t* __restrict__ s
   }
 }
 
-TTDK_EXPORT int ttdk_wprep(const bf16_t* src, bf16_t* dst, const void* tab, int n, int tiles, hipStream_t st) {
+TTDK_API(int, ttdk_wprep, (const bf16_t* src, bf16_t* dst, const void* tab, int n, int tiles, hipStream_t st)) {
   if (n <= 0 || tiles <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(wprep_kernel, dim3(tiles), dim3(256), 0, st, src, dst, static_cast<const WPrepEntry*>(tab), n);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_transpose2d_f32(const float* src, float* dst, int R, int C, hipStream_t st) {
+TTDK_API(int, ttdk_transpose2d_f32, (const float* src, float* dst, int R, int C, hipStream_t st)) {
   dim3 grid((C + 31) / 32, (R + 31) / 32);
   hipLaunchKernelGGL(transpose2d_f32_kernel, grid, dim3(256), 0, st, src, dst, R, C);
   return hipGetLastError();
 }
 
 // dtype 0 = fp32, 1 = bf16
-TTDK_EXPORT int ttdk_bias_act_dropout_fwd(const void* x, const float* bias, void* y, long long n, int C, int act,
+TTDK_API(int, ttdk_bias_act_dropout_fwd, (const void* x, const float* bias, void* y, long long n, int C, int act,
                                           float rate, unsigned long long seed, unsigned long long offset, int dtype,
-                                          hipStream_t st) {
+                                          hipStream_t st)) {
   if (dtype == 0)
     hipLaunchKernelGGL(bias_act_dropout_fwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st,
                        static_cast<const float*>(x), bias, static_cast<float*>(y), n, C, act, rate, seed, offset);
@@ -585,9 +585,9 @@ TTDK_EXPORT int ttdk_bias_act_dropout_fwd(const void* x, const float* bias, void
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bias_act_dropout_bwd(const void* dy, const void* x, const float* bias, void* dx, long long n,
+TTDK_API(int, ttdk_bias_act_dropout_bwd, (const void* dy, const void* x, const float* bias, void* dx, long long n,
                                           int C, int act, float rate, unsigned long long seed,
-                                          unsigned long long offset, int dtype, hipStream_t st) {
+                                          unsigned long long offset, int dtype, hipStream_t st)) {
   if (dtype == 0)
     hipLaunchKernelGGL(bias_act_dropout_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st,
                        static_cast<const float*>(dy), static_cast<const float*>(x), bias, static_cast<float*>(dx), n, C,
@@ -618,7 +618,7 @@ static void colsum_plan(long long rows, int C, int dtype, bool vec, long long* s
 }
 
 // Floats of workspace ttdk_colsum needs (covers both the vector and the scalar plan).
-TTDK_EXPORT long long ttdk_colsum_ws_floats(long long rows, int C, int dtype) {
+TTDK_API(long long, ttdk_colsum_ws_floats, (long long rows, int C, int dtype)) {
   long long s1, s2, per;
   colsum_plan(rows, C, dtype, true, &s1, &per);
   colsum_plan(rows, C, dtype, false, &s2, &per);
@@ -626,8 +626,8 @@ TTDK_EXPORT long long ttdk_colsum_ws_floats(long long rows, int C, int dtype) {
   return sl > 1 ? sl * C : 0;
 }
 
-TTDK_EXPORT int ttdk_colsum(const void* x, long long rows, int C, float* out, int beta, int dtype, float* ws,
-                            hipStream_t st) {
+TTDK_API(int, ttdk_colsum, (const void* x, long long rows, int C, float* out, int beta, int dtype, float* ws,
+                            hipStream_t st)) {
   const bool vec = dtype == 1 && C % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   long long slices, per;
   colsum_plan(rows, C, dtype, vec, &slices, &per);
@@ -657,14 +657,14 @@ TTDK_EXPORT int ttdk_colsum(const void* x, long long rows, int C, float* out, in
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_add_bf16(const bf16_t* a, const bf16_t* b, bf16_t* y, long long n, float alpha, float beta,
-                              hipStream_t st) {
+TTDK_API(int, ttdk_add_bf16, (const bf16_t* a, const bf16_t* b, bf16_t* y, long long n, float alpha, float beta,
+                              hipStream_t st)) {
   if (n % 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, a, b, y, n / 8, alpha, beta);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_amax_bf16(const bf16_t* x, long long n, float* amax, int reset, hipStream_t st) {
+TTDK_API(int, ttdk_amax_bf16, (const bf16_t* x, long long n, float* amax, int reset, hipStream_t st)) {
   if (reset) {
     hipError_t e = hipMemsetAsync(amax, 0, sizeof(float), st);
     if (e != hipSuccess) return e;
@@ -673,13 +673,13 @@ TTDK_EXPORT int ttdk_amax_bf16(const bf16_t* x, long long n, float* amax, int re
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_quant_fp8(const bf16_t* x, uint8_t* q, long long n, const float* scale, int e5m2, hipStream_t st) {
+TTDK_API(int, ttdk_quant_fp8, (const bf16_t* x, uint8_t* q, long long n, const float* scale, int e5m2, hipStream_t st)) {
   hipLaunchKernelGGL(quant_fp8_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, q, n, scale, e5m2);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_dequant_fp8(const uint8_t* q, bf16_t* x, long long n, const float* scale, int e5m2,
-                                 hipStream_t st) {
+TTDK_API(int, ttdk_dequant_fp8, (const uint8_t* q, bf16_t* x, long long n, const float* scale, int e5m2,
+                                 hipStream_t st)) {
   hipLaunchKernelGGL(dequant_fp8_kernel, dim3(grid_for(n)), dim3(256), 0, st, q, x, n, scale, e5m2);
   return hipGetLastError();
 }

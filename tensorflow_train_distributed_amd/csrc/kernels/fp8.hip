@@ -84,14 +84,14 @@ __global__ __launch_bounds__(256) void multi_quant_kernel(const bf16_t* __restri
 
 using namespace ttdk;
 
-TTDK_EXPORT int ttdk_fp8_rollover(float* slots, int n, float fmax, float margin, hipStream_t st) {
+TTDK_API(int, ttdk_fp8_rollover, (float* slots, int n, float fmax, float margin, hipStream_t st)) {
   hipLaunchKernelGGL(rollover_kernel, dim3((n + 255) / 256), dim3(256), 0, st, slots, n, fmax, margin);
   return hipGetLastError();
 }
 
 // table: device array of n_tensors {int64 offset, int32 len, int32 slot}; max_len bounds the grid.
-TTDK_EXPORT int ttdk_fp8_quant_weights(const bf16_t* src, uint8_t* dst, const void* table, int n_tensors, int max_len,
-                                       float* slots, int n_slots, hipStream_t st) {
+TTDK_API(int, ttdk_fp8_quant_weights, (const bf16_t* src, uint8_t* dst, const void* table, int n_tensors, int max_len,
+                                       float* slots, int n_slots, hipStream_t st)) {
   const QEntry* tab = static_cast<const QEntry*>(table);
   // amax_cur of the weight slots is rebuilt from scratch every call
   hipLaunchKernelGGL(rollover_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, st, slots, n_slots, 448.f, 1.f);

@@ -860,7 +860,7 @@ static int g4t_bm(int M, bool rowsum) {
 // floats of workspace ttdk_gemm4t_wgrad needs: split partial tiles + bias-gradient partials;
 // -1 when the kernel would refuse the shape (the same admission checks as ttdk_gemm4t_wgrad,
 // except the leading dimensions / pointers, with lda = M and ldb = N)
-TTDK_EXPORT long long ttdk_gemm4t_ws(int M, int N, int K, int splits) {
+TTDK_API(long long, ttdk_gemm4t_ws, (int M, int N, int K, int splits)) {
   using namespace ttdk;
   if (!g4t_enabled() || !plan::gemm4t_takes(M, N, K)) return -1;
   splits = plan::clamp_splits_4t(K / 64, splits);
@@ -872,9 +872,9 @@ TTDK_EXPORT long long ttdk_gemm4t_ws(int M, int N, int K, int splits) {
 // dW[M,N] (+)= alpha * A^T . B, A [K][M] (lda), B [K][N] (ldb) bf16 MN-major, out fp32 contiguous
 // [M][N]; rowsum (optional): bias gradient sum_k A[k][m], written. ws: ttdk_gemm4t_ws floats.
 // Returns hipErrorInvalidValue for shapes this kernel does not take (the caller keeps another path).
-TTDK_EXPORT int ttdk_gemm4t_wgrad(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
+TTDK_API(int, ttdk_gemm4t_wgrad, (const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
                                   int splits, float* ws, float* out, int beta, float alpha, float* rowsum,
-                                  hipStream_t st) {
+                                  hipStream_t st)) {
   using namespace ttdk;
   const long long lim = 1LL << 31;
   if (!g4t_enabled() || !plan::gemm4t_takes(M, N, K) || lda % 8 || ldb % 8 || lda < M || ldb < N || !al16(A) ||
@@ -935,7 +935,7 @@ ttdk::g4t::Gather conv_gather(const TtdkConv* g) {
 }  // namespace
 
 // floats of workspace ttdk_conv_wgrad4t needs (-1: the kernel does not take the conv)
-TTDK_EXPORT long long ttdk_conv_wgrad4t_ws(const TtdkConv* g, int splits) {
+TTDK_API(long long, ttdk_conv_wgrad4t_ws, (const TtdkConv* g, int splits)) {
   if (!ttdk::plan::conv_wgrad4t_takes(*g)) return -1;
   return ttdk_gemm4t_ws(g->K, g->R * g->S * g->C, g->N * g->P * g->Q, splits);
 }
@@ -944,8 +944,8 @@ TTDK_EXPORT long long ttdk_conv_wgrad4t_ws(const TtdkConv* g, int splits) {
 // transposed-read kernel: A = dy [pixels][K] (MN-major), B = x read through the im2col gather
 // (dense [pixels][C] for unit-stride 1x1 convs); split-K summed inside the launch (no fold pass).
 // ws: ttdk_conv_wgrad4t_ws floats. hipErrorInvalidValue: the kernel does not take the conv.
-TTDK_EXPORT int ttdk_conv_wgrad4t(const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
-                                  int splits, int beta, hipStream_t st) {
+TTDK_API(int, ttdk_conv_wgrad4t, (const bf16_t* x, const bf16_t* dy, const TtdkConv* g, float* dw, float* ws,
+                                  int splits, int beta, hipStream_t st)) {
   using namespace ttdk;
   if (ttdk_conv_wgrad4t_ws(g, splits) < 0 || !g4t_enabled()) return hipErrorInvalidValue;
   if (is_pointwise(g))
@@ -978,7 +978,7 @@ TTDK_EXPORT int ttdk_conv_wgrad4t(const bf16_t* x, const bf16_t* dy, const TtdkC
 // floats of workspace ttdk_conv_wgrad4t8 needs (-1: the fp8 kernel does not take the conv): C and
 // K multiples of 16 (16-B DMA chunks of 16 channels), >= 16 output rows / columns, pixels a
 // multiple of 128 (whole K-tiles), operands under 2 GiB (the gather's out-of-range offset)
-TTDK_EXPORT long long ttdk_conv_wgrad4t8_ws(const TtdkConv* g, int splits) {
+TTDK_API(long long, ttdk_conv_wgrad4t8_ws, (const TtdkConv* g, int splits)) {
   using namespace ttdk;
   if (!g4t_enabled() || !plan::conv_wgrad4t8_takes(*g)) return -1;
   const int M = g->K, N = g->R * g->S * g->C;
@@ -991,8 +991,8 @@ TTDK_EXPORT long long ttdk_conv_wgrad4t8_ws(const TtdkConv* g, int splits) {
 // ([pixels][C] for unit-stride 1x1 convs, else gathered), sa / sx the inverse quantisation scales
 // (device fp32); split-K summed inside the launch. ws: ttdk_conv_wgrad4t8_ws floats.
 // hipErrorInvalidValue: the kernel does not take the conv (the caller keeps conv_wgrad_fp8).
-TTDK_EXPORT int ttdk_conv_wgrad4t8(const uint8_t* x8, const uint8_t* dy8, const TtdkConv* g, float* dw, float* ws,
-                                   int splits, int beta, const float* sa, const float* sx, hipStream_t st) {
+TTDK_API(int, ttdk_conv_wgrad4t8, (const uint8_t* x8, const uint8_t* dy8, const TtdkConv* g, float* dw, float* ws,
+                                   int splits, int beta, const float* sa, const float* sx, hipStream_t st)) {
   using namespace ttdk;
   if (ttdk_conv_wgrad4t8_ws(g, splits) < 0 || !sa || !sx || !al16(x8) || !al16(dy8) || !al16(dw))
     return hipErrorInvalidValue;

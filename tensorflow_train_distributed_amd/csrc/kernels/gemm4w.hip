@@ -1209,7 +1209,7 @@ static int& g4_stagger() {
   static int v = ttdk::getenv_int("TTD_G4_STAGGER", 0);
   return v;
 }
-TTDK_EXPORT int ttdk_set_g4_stagger(int v) {
+TTDK_API(int, ttdk_set_g4_stagger, (int v)) {
   const int old = g4_stagger();
   g4_stagger() = v;
   return old;
@@ -1220,12 +1220,12 @@ static int& g4_group() {
   static int v = ttdk::getenv_int("TTD_G4_GROUP", 8);
   return v;
 }
-TTDK_EXPORT int ttdk_set_g4_group(int v) {
+TTDK_API(int, ttdk_set_g4_group, (int v)) {
   const int old = g4_group();
   g4_group() = v;
   return old;
 }
-TTDK_EXPORT int ttdk_set_g4_sched(int v) {
+TTDK_API(int, ttdk_set_g4_sched, (int v)) {
   const int old = g4_sched();
   g4_sched() = v;
   return old;
@@ -1237,8 +1237,8 @@ TTDK_EXPORT int ttdk_set_g4_sched(int v) {
 // rows: [2 ceil(M / 256)][2][K]. Unit-stride 1x1 convs read x as a dense [M][C] operand, the
 // others through the implicit-GEMM gather (g4::LoadConv). Needs C % 64 == 0 (a K-tile inside one
 // tap), R S C >= 128, no dilation. hipErrorInvalidValue: not taken (the caller keeps conv_fwd).
-TTDK_EXPORT int ttdk_conv_fwd4w(const bf16_t* x, const bf16_t* w, const TtdkConv* g, const TtdkEpilogue* epi,
-                                hipStream_t st) {
+TTDK_API(int, ttdk_conv_fwd4w, (const bf16_t* x, const bf16_t* w, const TtdkConv* g, const TtdkEpilogue* epi,
+                                hipStream_t st)) {
   using namespace ttdk;
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->P * g->Q, N = g->K, K = g->R * g->S * g->C;
@@ -1276,8 +1276,8 @@ TTDK_EXPORT int ttdk_conv_fwd4w(const bf16_t* x, const bf16_t* w, const TtdkConv
 // ldo = C, and either nothing else (plain store) or the feeding-BN epilogue (by, bmask, stat:
 // g = dx * ReLU bits stored, partial sums (sum g, sum g * y) per 128 rows, [2 ceil(M / 256)][2][C]).
 // Needs K % 64 == 0 (dy channels), R S K >= 128. hipErrorInvalidValue: not taken.
-TTDK_EXPORT int ttdk_conv_dgrad4w(const bf16_t* dy, const bf16_t* wt, const TtdkConv* g, const TtdkEpilogue* epi,
-                                  hipStream_t st) {
+TTDK_API(int, ttdk_conv_dgrad4w, (const bf16_t* dy, const bf16_t* wt, const TtdkConv* g, const TtdkEpilogue* epi,
+                                  hipStream_t st)) {
   using namespace ttdk;
   EpiParams pe = to_epi(epi);
   const int M = g->N * g->H * g->W, N = g->C, K = g->R * g->S * g->K;
@@ -1302,8 +1302,8 @@ TTDK_EXPORT int ttdk_conv_dgrad4w(const bf16_t* dy, const bf16_t* wt, const Ttdk
 // C[M,N] = epilogue(alpha * A . B^T), A [M][K] (lda), B [N][K] (ldb) bf16 K-major; K % 64 == 0,
 // N % 8 == 0, ldo % 8 == 0, 16-B aligned operands and outputs. Returns hipErrorInvalidValue for
 // shapes this kernel does not take (the caller keeps another path).
-TTDK_EXPORT int ttdk_gemm4w_bf16(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
-                                 const TtdkEpilogue* epi, hipStream_t st) {
+TTDK_API(int, ttdk_gemm4w_bf16, (const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
+                                 const TtdkEpilogue* epi, hipStream_t st)) {
   using namespace ttdk;
   EpiParams pe = to_epi(epi);
   const long long lim = 1LL << 32;
@@ -1379,8 +1379,8 @@ TTDK_EXPORT int ttdk_gemm4w_bf16(const bf16_t* A, long long lda, const bf16_t* B
 // of the stored output per 128 rows, [2 ceil(M / 256)][2][K]. Needs C % 128 == 0, K % 8 == 0,
 // no dilation, operands under 2 GiB. hipErrorInvalidValue: not taken (the caller keeps the 8-wave
 // conv_fwd_fp8).
-TTDK_EXPORT int ttdk_conv_fwd4k8(const uint8_t* x8, const uint8_t* w8, const TtdkConv* g, bf16_t* out, float* stat,
-                                 const float* sa, const float* sw, hipStream_t st) {
+TTDK_API(int, ttdk_conv_fwd4k8, (const uint8_t* x8, const uint8_t* w8, const TtdkConv* g, bf16_t* out, float* stat,
+                                 const float* sa, const float* sw, hipStream_t st)) {
   using namespace ttdk;
   const int M = g->N * g->P * g->Q, N = g->K, K = g->R * g->S * g->C;
   const long long xb = static_cast<long long>(g->N) * g->H * g->W * g->C;
@@ -1418,9 +1418,9 @@ TTDK_EXPORT int ttdk_conv_fwd4k8(const uint8_t* x8, const uint8_t* w8, const Ttd
 // else a plain store; beta (with the feeding epilogue only): g = (dx + out) * bits. Needs K % 128 == 0
 // (the gradient's channels), C % 8 == 0.
 // hipErrorInvalidValue: not taken (the caller keeps conv_dgrad_fp8's 8-wave kernel).
-TTDK_EXPORT int ttdk_conv_dgrad4k8(const uint8_t* dy8, const uint8_t* wt8, const TtdkConv* g, bf16_t* out,
+TTDK_API(int, ttdk_conv_dgrad4k8, (const uint8_t* dy8, const uint8_t* wt8, const TtdkConv* g, bf16_t* out,
                                    const bf16_t* by, const uint8_t* bmask, float* stat, int beta, const float* sa,
-                                   const float* sw, hipStream_t st) {
+                                   const float* sw, hipStream_t st)) {
   using namespace ttdk;
   const int M = g->N * g->H * g->W, N = g->C, K = g->R * g->S * g->K;
   const long long yb = static_cast<long long>(g->N) * g->P * g->Q * g->K;

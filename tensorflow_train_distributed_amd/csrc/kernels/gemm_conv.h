@@ -2660,6 +2660,10 @@ struct TtdkEpilogue {
   float* stat2;
   int bH, bW;            // EpiParams::bH/bW (stride-2-sampled beta)
 };
+template <>
+struct ttd_abi::Code<const TtdkEpilogue*> {
+  static constexpr char code = 'E';
+};
 
 inline EpiParams to_epi(const TtdkEpilogue* e) {
   EpiParams p;

@@ -10,9 +10,9 @@ extern "C" int ttdk_gemm4w_bf16(const bf16_t* A, long long lda, const bf16_t* B,
 
 // General GEMM: C[M,N] = alpha * A·B with A either K-major (a_kmajor=1: A[m*lda + k]) or
 // MN-major (A[k*lda + m]); B either K-major (B[n*ldb + k]) or MN-major (B[k*ldb + n]).
-TTDK_EXPORT int ttdk_gemm_bf16(const bf16_t* A, long long lda, int a_kmajor, const bf16_t* B, long long ldb,
+TTDK_API(int, ttdk_gemm_bf16, (const bf16_t* A, long long lda, int a_kmajor, const bf16_t* B, long long ldb,
                                int b_kmajor, int M, int N, int K, int splits, int bm, int bn,
-                               const TtdkEpilogue* epi, hipStream_t st) {
+                               const TtdkEpilogue* epi, hipStream_t st)) {
   EpiParams pe = to_epi(epi);
   // 16-B vector operand loads need the contiguous dim and the leading dim to be multiples
   // of 8 elements and 16-B aligned bases; otherwise both operands use the masked scalar path.
@@ -58,9 +58,9 @@ TTDK_EXPORT int ttdk_gemm_bf16(const bf16_t* A, long long lda, int a_kmajor, con
 // grid z; A_z = A + z*sa, B_z = B + z*sb, C_z = out + z*so, element strides), bf16 operands in
 // either layout, bf16 (out_fp32 = 0) or fp32 output. The batched MatMul of ttd.nn.matmul
 // (tf.matmul on rank > 2 operands; per-entry launches before).
-TTDK_EXPORT int ttdk_gemm_bf16_batched(const bf16_t* A, long long lda, long long sa, int a_kmajor, const bf16_t* B,
+TTDK_API(int, ttdk_gemm_bf16_batched, (const bf16_t* A, long long lda, long long sa, int a_kmajor, const bf16_t* B,
                                        long long ldb, long long sb, int b_kmajor, void* out, long long ldo,
-                                       long long so, int out_fp32, int M, int N, int K, int batch, hipStream_t st) {
+                                       long long so, int out_fp32, int M, int N, int K, int batch, hipStream_t st)) {
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch > 65535) return hipErrorInvalidValue;
   const bool vec = al16(A) && al16(B) && lda % 8 == 0 && ldb % 8 == 0 && sa % 8 == 0 && sb % 8 == 0 &&
                    (a_kmajor ? K % 8 == 0 : M % 8 == 0) && (b_kmajor ? K % 8 == 0 : N % 8 == 0);
@@ -101,9 +101,9 @@ TTDK_EXPORT int ttdk_gemm_bf16_batched(const bf16_t* A, long long lda, long long
 // Split-K GEMM into an fp32 output: C (+)= alpha * A.B over `splits` K-slices with fp32 slabs in
 // `ws` [splits][M][N]. On the 256-row kernel the launch folds its own slabs (EpiParams mode 3);
 // elsewhere a fold pass follows.
-TTDK_EXPORT int ttdk_gemm_bf16_splitk(const bf16_t* A, long long lda, int a_kmajor, const bf16_t* B, long long ldb,
+TTDK_API(int, ttdk_gemm_bf16_splitk, (const bf16_t* A, long long lda, int a_kmajor, const bf16_t* B, long long ldb,
                                       int b_kmajor, int M, int N, int K, int splits, float* ws, float* out, int beta,
-                                      float alpha, int tile_m, int tile_n, hipStream_t st) {
+                                      float alpha, int tile_m, int tile_n, hipStream_t st)) {
   TtdkEpilogue te{};
   te.mode = 1;
   te.out = ws;
@@ -146,7 +146,7 @@ TTDK_EXPORT int ttdk_gemm_bf16_splitk(const bf16_t* A, long long lda, int a_kmaj
 // column-sum pass over dY disappears. ws: splits * M * N floats (split-K slabs) followed by
 // splits * ceil(N / 256) * M floats (row-sum partials). Returns hipErrorInvalidValue when the
 // shape does not take the 256-row ping-pong kernel (the caller keeps its column-sum pass).
-TTDK_EXPORT long long ttdk_gemm_wgrad_bias_ws(int M, int N, int K, int splits) {
+TTDK_API(long long, ttdk_gemm_wgrad_bias_ws, (int M, int N, int K, int splits)) {
   // -1 (no fused path: the caller keeps its column-sum pass) unless gemm4t or the 256-row
   // kernel admits the shape
   const long long w4 = ttdk_gemm4t_ws(M, N, K, splits);
@@ -156,9 +156,9 @@ TTDK_EXPORT long long ttdk_gemm_wgrad_bias_ws(int M, int N, int K, int splits) {
   return std::max(w4, static_cast<long long>(splits) * M * N + static_cast<long long>(splits) * ceil_div(N, 256) * M);
 }
 
-TTDK_EXPORT int ttdk_gemm_wgrad_bias(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
+TTDK_API(int, ttdk_gemm_wgrad_bias, (const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
                                      int splits, float* ws, float* out, int beta, float alpha, float* rowsum,
-                                     hipStream_t st) {
+                                     hipStream_t st)) {
   {
     const int rc = ttdk_gemm4t_wgrad(A, lda, B, ldb, M, N, K, splits, ws, out, beta, alpha, rowsum, st);
     if (rc != hipErrorInvalidValue) return rc;
@@ -184,7 +184,7 @@ TTDK_EXPORT int ttdk_gemm_wgrad_bias(const bf16_t* A, long long lda, const bf16_
   return splitk_reduce(rs, splits * ceil_div(N, 256), M, rowsum, 0, st);
 }
 
-TTDK_EXPORT int ttdk_splitk_reduce(const float* ws, int splits, long long n, float* out, int beta, hipStream_t st) {
+TTDK_API(int, ttdk_splitk_reduce, (const float* ws, int splits, long long n, float* out, int beta, hipStream_t st)) {
   return splitk_reduce(ws, splits, n, out, beta, st);
 }
 
@@ -206,7 +206,7 @@ int& fold_flag() {
 
 // Runtime switch of the in-kernel split-K fold (gemm_conv.h inkernel_fold); returns the previous
 // setting.
-TTDK_EXPORT int ttdk_set_inkernel_fold(int on) {
+TTDK_API(int, ttdk_set_inkernel_fold, (int on)) {
   const int old = ttdk_rt::fold_flag();
   ttdk_rt::fold_flag() = on;
   return old;
@@ -214,19 +214,19 @@ TTDK_EXPORT int ttdk_set_inkernel_fold(int on) {
 
 // CUs kept free of persistent grids for the collective engine's CTAs (see device_cus in
 // gemm_conv.h); returns the previous setting.
-TTDK_EXPORT int ttdk_set_reserved_cus(int n) {
+TTDK_API(int, ttdk_set_reserved_cus, (int n)) {
   const int old = ttdk_rt::reserved_cus();
   ttdk_rt::reserved_cus() = n < 0 ? 0 : n;
   return old;
 }
 
 // CUs the persistent kernels currently size their grids to.
-TTDK_EXPORT int ttdk_persistent_cus() { return big::device_cus(); }
+TTDK_API(int, ttdk_persistent_cus, ()) { return big::device_cus(); }
 
 
 // Runtime switch of the persistent register-epilogue 256-row GEMM (gemm256p_kernel); returns
 // the previous setting.
-TTDK_EXPORT int ttdk_set_big_pers(int on) {
+TTDK_API(int, ttdk_set_big_pers, (int on)) {
   const int old = ttdk_rt::pers_flag();
   ttdk_rt::pers_flag() = on;
   return old;

@@ -93,8 +93,8 @@ using namespace ttdk;
 
 // C[M,N] (row stride ldc) = op(A) . op(B) (+ bias) (+ C if beta); ta/tb: A stored [K][M] / B
 // stored [N][K]. All fp32, exact f32 products (f32 MFMA).
-TTDK_EXPORT int ttdk_gemm_f32(const float* A, long long lda, int ta, const float* B, long long ldb, int tb, float* C,
-                              long long ldc, const float* bias, int beta, int M, int N, int K, hipStream_t st) {
+TTDK_API(int, ttdk_gemm_f32, (const float* A, long long lda, int ta, const float* B, long long ldb, int tb, float* C,
+                              long long ldc, const float* bias, int beta, int M, int N, int K, hipStream_t st)) {
   if (M <= 0 || N <= 0 || K < 0) return hipErrorInvalidValue;
   dim3 grid(ceil_div(N, F_BN), ceil_div(M, F_BM));
   hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(F_THR), 0, st, A, lda, ta, B, ldb, tb, C, ldc, bias, beta, M, N, K);
@@ -103,9 +103,9 @@ TTDK_EXPORT int ttdk_gemm_f32(const float* A, long long lda, int ta, const float
 
 // Strided-batched form: `batch` GEMMs in one launch (entry z reads A + z*sa, B + z*sb, writes
 // C + z*sc; element strides). The batched MatMul of ttd.nn.matmul on rank > 2 fp32 operands.
-TTDK_EXPORT int ttdk_gemm_f32_batched(const float* A, long long lda, long long sa, int ta, const float* B, long long ldb,
+TTDK_API(int, ttdk_gemm_f32_batched, (const float* A, long long lda, long long sa, int ta, const float* B, long long ldb,
                                       long long sb, int tb, float* C, long long ldc, long long sc, int M, int N, int K,
-                                      int batch, hipStream_t st) {
+                                      int batch, hipStream_t st)) {
   if (M <= 0 || N <= 0 || K < 0 || batch <= 0 || batch > 65535) return hipErrorInvalidValue;
   dim3 grid(ceil_div(N, F_BN), ceil_div(M, F_BM), batch);
   hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(F_THR), 0, st, A, lda, ta, B, ldb, tb, C, ldc, nullptr, 0, M, N, K, sa,

@@ -7,12 +7,18 @@
 // paths before it calls a launcher; tests/test_gemm_plan.py pins them on the CPU. Environment
 // switches are read by the callers and passed in; pointer and epilogue checks stay in the launchers.
 
+#include "abi.h"
+
 // Convolution geometry passed from Python (ops/_lib.py ConvGeom, identical layout).
 struct TtdkConv {
   int N, H, W, C;   // input NHWC
   int K, R, S;      // filters [K][R][S][C]
   int P, Q;         // output spatial
   int sh, sw, ph, pw, dh, dw;
+};
+template <>
+struct ttd_abi::Code<const TtdkConv*> {
+  static constexpr char code = 'G';
 };
 
 namespace ttdk {

@@ -514,9 +514,9 @@ using namespace ttdk;
 
 // y, mean [N,G], rstd [N,G] of x [N,M,C] (type dt). gamma / beta: fp32 [C] or null. ws: 16-byte
 // aligned fp32 workspace of at least gnplan::fwd_ws_floats(N, M, C) floats.
-TTDK_EXPORT int ttdk_group_norm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
+TTDK_API(int, ttdk_group_norm_fwd, (const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                     float* rstd, float* ws, long long ws_floats, long long N, long long M, int C, int G,
-                                    float eps, int dt, int form, hipStream_t st) {
+                                    float eps, int dt, int form, hipStream_t st)) {
   if (!gnplan::valid(N, M, C, G) || !x || !y || !mean || !rstd || !ws || (dt != 0 && dt != 1)) return hipErrorInvalidValue;
   if (!aligned16(ws) || ws_floats < gnplan::fwd_ws_floats(N, M, C)) return hipErrorInvalidValue;
   if (form == 0 && gnplan::fast_takes(N, M, C, G, dt) && aligned16(x) && aligned16(y) && aligned16(beta))
@@ -528,10 +528,10 @@ TTDK_EXPORT int ttdk_group_norm_fwd(const void* x, const float* gamma, const flo
 // The sums of the backward: dgamma / dbeta fp32 [C] (either may be null; (+)= with accumulate) and,
 // left in ws for ttdk_group_norm_bwd_dx, the coefficient rows of dx. ws: 16-byte aligned, at least
 // gnplan::bwd_ws_floats(N, M, C) floats.
-TTDK_EXPORT int ttdk_group_norm_bwd_stats(const void* dy, const void* x, const float* gamma, const float* mean,
+TTDK_API(int, ttdk_group_norm_bwd_stats, (const void* dy, const void* x, const float* gamma, const float* mean,
                                           const float* rstd, float* dgamma, float* dbeta, float* ws, long long ws_floats,
                                           long long N, long long M, int C, int G, int dt, int accumulate, int form,
-                                          hipStream_t st) {
+                                          hipStream_t st)) {
   if (!gnplan::valid(N, M, C, G) || !dy || !x || !mean || !rstd || !ws || (dt != 0 && dt != 1))
     return hipErrorInvalidValue;
   if (!aligned16(ws) || ws_floats < gnplan::bwd_ws_floats(N, M, C)) return hipErrorInvalidValue;
@@ -543,8 +543,8 @@ TTDK_EXPORT int ttdk_group_norm_bwd_stats(const void* dy, const void* x, const f
 }
 
 // dx from the coefficient rows ttdk_group_norm_bwd_stats left in the same ws.
-TTDK_EXPORT int ttdk_group_norm_bwd_dx(const void* dy, const void* x, const float* ws, long long ws_floats, void* dx,
-                                       long long N, long long M, int C, int G, int dt, int form, hipStream_t st) {
+TTDK_API(int, ttdk_group_norm_bwd_dx, (const void* dy, const void* x, const float* ws, long long ws_floats, void* dx,
+                                       long long N, long long M, int C, int G, int dt, int form, hipStream_t st)) {
   if (!gnplan::valid(N, M, C, G) || !dy || !x || !dx || !ws || (dt != 0 && dt != 1)) return hipErrorInvalidValue;
   if (!aligned16(ws) || ws_floats < gnplan::bwd_ws_floats(N, M, C)) return hipErrorInvalidValue;
   if (form == 0 && gnplan::fast_takes(N, M, C, G, dt) && aligned16(dy) && aligned16(x) && aligned16(dx))

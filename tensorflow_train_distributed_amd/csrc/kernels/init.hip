@@ -58,8 +58,8 @@ __global__ void init_random_kernel(float* __restrict__ out, long long n, int dis
 
 using namespace ttdk;
 
-TTDK_EXPORT int ttdk_init_random(float* out, long long n, int dist, float a, float b, unsigned long long seed,
-                                 unsigned long long offset, hipStream_t st) {
+TTDK_API(int, ttdk_init_random, (float* out, long long n, int dist, float a, float b, unsigned long long seed,
+                                 unsigned long long offset, hipStream_t st)) {
   if (n < 0 || dist < 0 || dist > 3) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   long long blocks = (n + 255) / 256;

@@ -233,7 +233,7 @@ using ttdk::IpcEngine;
 
 // Staging buffers of `cap_bytes` per region on `device` (4 regions) + flags. spin_max: barrier
 // polls before a peer counts as lost (<= 0: the default, ~1-2 s). Returns null on failure.
-TTDK_EXPORT void* ttdi_create(int rank, int world, int device, long long cap_bytes, long long spin_max) {
+TTDK_API(void*, ttdi_create, (int rank, int world, int device, long long cap_bytes, long long spin_max)) {
   static_assert(sizeof(hipIpcMemHandle_t) == ttdk::kHandleBytes, "IPC handle size");
   if (world < 1 || world > ttdk::kMaxRanks || rank < 0 || rank >= world || cap_bytes <= 0) return nullptr;
   if (hipSetDevice(device) != hipSuccess) return nullptr;
@@ -275,7 +275,7 @@ TTDK_EXPORT void* ttdi_create(int rank, int world, int device, long long cap_byt
 }
 
 // This rank's IPC handles: out[0:64] data, out[64:128] flags.
-TTDK_EXPORT int ttdi_handle(void* h, char* out) {
+TTDK_API(int, ttdi_handle, (void* h, char* out)) {
   auto* e = static_cast<IpcEngine*>(h);
   hipIpcMemHandle_t a, f;
   hipError_t rc = hipIpcGetMemHandle(&a, e->data);
@@ -289,7 +289,7 @@ TTDK_EXPORT int ttdi_handle(void* h, char* out) {
 
 // Map every peer: handles = world x 128 bytes (ttdi_handle of each rank, rank order), devices =
 // each rank's device ordinal (peer access is enabled for the other devices of this node).
-TTDK_EXPORT int ttdi_open(void* h, const char* handles, const int* devices) {
+TTDK_API(int, ttdi_open, (void* h, const char* handles, const int* devices)) {
   auto* e = static_cast<IpcEngine*>(h);
   if (hipSetDevice(e->device) != hipSuccess) return hipErrorInvalidDevice;
   for (int p = 0; p < e->world; ++p) {
@@ -324,7 +324,7 @@ TTDK_EXPORT int ttdi_open(void* h, const char* handles, const int* devices) {
 // Test helper: make engine `other` (another rank's engine in THIS process, same device) a peer
 // of `h` without IPC — one process can then run every rank of a small group on one GPU (each
 // rank's kernel on its own stream) to check the barriers and the two-shot exchange.
-TTDK_EXPORT int ttdi_link_local(void* h, void* other) {
+TTDK_API(int, ttdi_link_local, (void* h, void* other)) {
   auto* e = static_cast<IpcEngine*>(h);
   auto* o = static_cast<IpcEngine*>(other);
   if (o->world != e->world || o->rank == e->rank || o->device != e->device) return hipErrorInvalidValue;
@@ -338,8 +338,8 @@ TTDK_EXPORT int ttdi_link_local(void* h, void* other) {
 // budget; <= 0: ttd_ipc::kMaxBlocks). Every rank must call with the same count / path /
 // max_blocks in the same order. The bucket is processed in whole 16-B vectors (count % (16 B /
 // element) == 0, 16-B aligned).
-TTDK_EXPORT int ttdi_allreduce(void* h, void* buf, long long count, int dtype, int path, int max_blocks,
-                               hipStream_t st) {
+TTDK_API(int, ttdi_allreduce, (void* h, void* buf, long long count, int dtype, int path, int max_blocks,
+                               hipStream_t st)) {
   auto* e = static_cast<IpcEngine*>(h);
   const int esz = dtype == 0 ? 4 : 2, vec = 16 / esz;
   const long long bytes = count * esz;
@@ -362,14 +362,14 @@ TTDK_EXPORT int ttdi_allreduce(void* h, void* buf, long long count, int dtype, i
 
 // 1 when a barrier of some call that has run so far timed out (a peer never arrived): the host
 // word the kernels write, read without any device synchronisation.
-TTDK_EXPORT int ttdi_error(void* h) {
+TTDK_API(int, ttdi_error, (void* h)) {
   auto* e = static_cast<IpcEngine*>(h);
   return *reinterpret_cast<volatile int*>(e->err);
 }
 
 // Clear the error word (tests; a recovered session builds a fresh engine instead). The caller
 // makes sure no launch of this engine is still running.
-TTDK_EXPORT void ttdi_clear_error(void* h) {
+TTDK_API(void, ttdi_clear_error, (void* h)) {
   auto* e = static_cast<IpcEngine*>(h);
   (void)hipSetDevice(e->device);
   (void)hipMemset(e->flags + ttdk::kAbortIdx, 0, sizeof(unsigned));
@@ -377,7 +377,7 @@ TTDK_EXPORT void ttdi_clear_error(void* h) {
   *reinterpret_cast<volatile int*>(e->err) = 0;
 }
 
-TTDK_EXPORT void ttdi_destroy(void* h) {
+TTDK_API(void, ttdi_destroy, (void* h)) {
   auto* e = static_cast<IpcEngine*>(h);
   if (!e) return;
   (void)hipSetDevice(e->device);

@@ -390,7 +390,7 @@ using namespace ttdk;
   } while (0)
 
 // number of row blocks the column-statistics kernel splits M rows into
-TTDK_EXPORT int ttdk_col_stats_parts(long long M, int C) {
+TTDK_API(int, ttdk_col_stats_parts, (long long M, int C)) {
   const long long cb = (C + 63) / 64;
   long long t = (M + 255) / 256;
   const long long cap = 2048 / cb > 1 ? 2048 / cb : 1;
@@ -399,8 +399,8 @@ TTDK_EXPORT int ttdk_col_stats_parts(long long M, int C) {
 }
 
 // mode 0: (sum a, sum a^2); mode 1: (sum a, sum a*b); mode 2: (sum a, sum a*(b-mu[r])*rs[r])
-TTDK_EXPORT int ttdk_col_stats(const void* a, const void* b, const float* mu, const float* rs, int dt, int mode,
-                               long long M, int C, float* part, int T, hipStream_t st) {
+TTDK_API(int, ttdk_col_stats, (const void* a, const void* b, const float* mu, const float* rs, int dt, int mode,
+                               long long M, int C, float* part, int T, hipStream_t st)) {
   if (C <= 0 || M <= 0 || T <= 0 || (mode != 0 && !b) || (mode == 2 && (!mu || !rs))) return hipErrorInvalidValue;
   const long long rpb = (M + T - 1) / T;
   dim3 grid((C + 63) / 64, T), block(256);
@@ -419,13 +419,13 @@ TTDK_EXPORT int ttdk_col_stats(const void* a, const void* b, const float* mu, co
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_col_reduce2(const float* part, int T, int C, float* o0, float* o1, int acc, hipStream_t st) {
+TTDK_API(int, ttdk_col_reduce2, (const float* part, int T, int C, float* o0, float* o1, int acc, hipStream_t st)) {
   hipLaunchKernelGGL(col_reduce2_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, T, C, o0, o1, acc);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_col_affine(const void* a, const void* b, int dt, const float* c0, const float* c1, const float* c2,
-                                void* out, long long n, int C, hipStream_t st) {
+TTDK_API(int, ttdk_col_affine, (const void* a, const void* b, int dt, const float* c0, const float* c1, const float* c2,
+                                void* out, long long n, int C, hipStream_t st)) {
   if (C <= 0 || (b && !c1)) return hipErrorInvalidValue;
   if (dt == 0)
     hipLaunchKernelGGL(col_affine_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)a, (const float*)b,
@@ -438,21 +438,21 @@ TTDK_EXPORT int ttdk_col_affine(const void* a, const void* b, int dt, const floa
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bn_infer_coef(const float* mm, const float* mv, const float* gamma, const float* beta, float eps,
-                                   int C, float* scale, float* shift, float* rstd, hipStream_t st) {
+TTDK_API(int, ttdk_bn_infer_coef, (const float* mm, const float* mv, const float* gamma, const float* beta, float eps,
+                                   int C, float* scale, float* shift, float* rstd, hipStream_t st)) {
   hipLaunchKernelGGL(bn_infer_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mm, mv, gamma, beta, eps, C, scale,
                      shift, rstd);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_bn_infer_bwd(const float* part, int T, int C, const float* mm, const float* rstd, float* dgamma,
-                                  float* dbeta, hipStream_t st) {
+TTDK_API(int, ttdk_bn_infer_bwd, (const float* part, int T, int C, const float* mm, const float* rstd, float* dgamma,
+                                  float* dbeta, hipStream_t st)) {
   hipLaunchKernelGGL(bn_infer_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, T, C, mm, rstd, dgamma, dbeta);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_maxpool_generic_fwd(const void* x, void* y, uint8_t* arg, int dt, int N, int H, int W, int C, int P,
-                                         int Q, int R, int S, int sh, int sw, int ph, int pw, hipStream_t st) {
+TTDK_API(int, ttdk_maxpool_generic_fwd, (const void* x, void* y, uint8_t* arg, int dt, int N, int H, int W, int C, int P,
+                                         int Q, int R, int S, int sh, int sw, int ph, int pw, hipStream_t st)) {
   if (R * S > 255 || ph >= R || pw >= S || P <= 0 || Q <= 0) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(N) * P * Q * C;
   if (dt == 0)
@@ -466,9 +466,9 @@ TTDK_EXPORT int ttdk_maxpool_generic_fwd(const void* x, void* y, uint8_t* arg, i
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_maxpool_generic_bwd(const void* dy, const uint8_t* arg, void* dx, int dt, int N, int H, int W,
+TTDK_API(int, ttdk_maxpool_generic_bwd, (const void* dy, const uint8_t* arg, void* dx, int dt, int N, int H, int W,
                                          int C, int P, int Q, int R, int S, int sh, int sw, int ph, int pw,
-                                         hipStream_t st) {
+                                         hipStream_t st)) {
   const long long total = static_cast<long long>(N) * H * W * C;
   if (dt == 0)
     hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)dy, arg,
@@ -481,29 +481,29 @@ TTDK_EXPORT int ttdk_maxpool_generic_bwd(const void* dy, const uint8_t* arg, voi
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_gap_fwd(const void* x, void* y, int dt, int N, int HW, int C, hipStream_t st) {
+TTDK_API(int, ttdk_gap_fwd, (const void* x, void* y, int dt, int N, int HW, int C, hipStream_t st)) {
   if (N <= 0 || N > 65535 || HW <= 0 || C <= 0) return hipErrorInvalidValue;
   dim3 grid((C + 63) / 64, N);
   TTDK_LAUNCH_DT(dt, gap_fwd_kernel, grid, dim3(256), (const TT*)x, (TT*)y, HW, C);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_gap_bwd(const void* dy, void* dx, int dt, int N, int HW, int C, hipStream_t st) {
+TTDK_API(int, ttdk_gap_bwd, (const void* dy, void* dx, int dt, int N, int HW, int C, hipStream_t st)) {
   const long long total = static_cast<long long>(N) * HW * C;
   TTDK_LAUNCH_DT(dt, gap_bwd_kernel, dim3(grid_for(total)), dim3(256), (const TT*)dy, (TT*)dx, total, HW, C);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_ln_generic_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd,
-                                    int dt, long long rows, int H, float eps, hipStream_t st) {
+TTDK_API(int, ttdk_ln_generic_fwd, (const void* x, const float* g, const float* b, void* y, float* mean, float* rstd,
+                                    int dt, long long rows, int H, float eps, hipStream_t st)) {
   if (H <= 0 || rows <= 0) return hipErrorInvalidValue;
   dim3 grid(static_cast<unsigned>((rows + 3) / 4));
   TTDK_LAUNCH_DT(dt, ln_fwd_kernel, grid, dim3(256), (const TT*)x, g, b, (TT*)y, mean, rstd, rows, H, eps);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_ln_generic_bwd_dx(const void* dy, const void* x, const float* g, const float* mean,
-                                       const float* rstd, void* dx, int dt, long long rows, int H, hipStream_t st) {
+TTDK_API(int, ttdk_ln_generic_bwd_dx, (const void* dy, const void* x, const float* g, const float* mean,
+                                       const float* rstd, void* dx, int dt, long long rows, int H, hipStream_t st)) {
   if (H <= 0 || rows <= 0) return hipErrorInvalidValue;
   dim3 grid(static_cast<unsigned>((rows + 3) / 4));
   TTDK_LAUNCH_DT(dt, ln_bwd_dx_kernel, grid, dim3(256), (const TT*)dy, (const TT*)x, g, mean, rstd, (TT*)dx, rows, H);
@@ -511,8 +511,8 @@ TTDK_EXPORT int ttdk_ln_generic_bwd_dx(const void* dy, const void* x, const floa
 }
 
 // ids: int32 (id64 = 0) or int64 (id64 = 1)
-TTDK_EXPORT int ttdk_gather_generic(const void* table, const void* ids, int id64, void* out, int dt, long long n, int H,
-                                    long long V, hipStream_t st) {
+TTDK_API(int, ttdk_gather_generic, (const void* table, const void* ids, int id64, void* out, int dt, long long n, int H,
+                                    long long V, hipStream_t st)) {
   const unsigned g = grid_for(n * H);
   if (dt == 0 && id64) hipLaunchKernelGGL((gather_kernel<float, long long>), dim3(g), dim3(256), 0, st, (const float*)table, (const long long*)ids, (float*)out, n, H, V);
   else if (dt == 0) hipLaunchKernelGGL((gather_kernel<float, int>), dim3(g), dim3(256), 0, st, (const float*)table, (const int*)ids, (float*)out, n, H, V);
@@ -523,8 +523,8 @@ TTDK_EXPORT int ttdk_gather_generic(const void* table, const void* ids, int id64
 }
 
 // dtable (fp32 [V][H]) += scatter(dy) — accumulates, so zero it first for a fresh gradient
-TTDK_EXPORT int ttdk_scatter_add_generic(const void* dy, const void* ids, int id64, float* dtable, int dt, long long n,
-                                         int H, long long V, hipStream_t st) {
+TTDK_API(int, ttdk_scatter_add_generic, (const void* dy, const void* ids, int id64, float* dtable, int dt, long long n,
+                                         int H, long long V, hipStream_t st)) {
   const unsigned g = grid_for(n * H);
   if (dt == 0 && id64) hipLaunchKernelGGL((scatter_add_kernel<float, long long>), dim3(g), dim3(256), 0, st, (const float*)dy, (const long long*)ids, dtable, n, H, V);
   else if (dt == 0) hipLaunchKernelGGL((scatter_add_kernel<float, int>), dim3(g), dim3(256), 0, st, (const float*)dy, (const int*)ids, dtable, n, H, V);
@@ -534,8 +534,8 @@ TTDK_EXPORT int ttdk_scatter_add_generic(const void* dy, const void* ids, int id
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_in_top_k(const void* z, const void* tgt, int id64, uint8_t* out, int dt, long long rows, int V,
-                              int k, hipStream_t st) {
+TTDK_API(int, ttdk_in_top_k, (const void* z, const void* tgt, int id64, uint8_t* out, int dt, long long rows, int V,
+                              int k, hipStream_t st)) {
   if (V <= 0 || rows <= 0) return hipErrorInvalidValue;
   const dim3 g(static_cast<unsigned>((rows + 3) / 4));
   if (dt == 0 && id64) hipLaunchKernelGGL((in_top_k_kernel<float, long long>), g, dim3(256), 0, st, (const float*)z, (const long long*)tgt, out, rows, V, k);
@@ -547,51 +547,51 @@ TTDK_EXPORT int ttdk_in_top_k(const void* z, const void* tgt, int id64, uint8_t*
 }
 
 // op 0 = tanh, 1 = sigmoid
-TTDK_EXPORT int ttdk_unary(const void* x, void* y, int dt, long long n, int op, hipStream_t st) {
+TTDK_API(int, ttdk_unary, (const void* x, void* y, int dt, long long n, int op, hipStream_t st)) {
   if (op < 0 || op > 1) return hipErrorInvalidValue;
   TTDK_LAUNCH_DT(dt, unary_kernel, dim3(grid_for(n)), dim3(256), (const TT*)x, (TT*)y, n, op);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_unary_bwd(const void* dy, const void* y, void* dx, int dt, long long n, int op, hipStream_t st) {
+TTDK_API(int, ttdk_unary_bwd, (const void* dy, const void* y, void* dx, int dt, long long n, int op, hipStream_t st)) {
   if (op < 0 || op > 1) return hipErrorInvalidValue;
   TTDK_LAUNCH_DT(dt, unary_bwd_kernel, dim3(grid_for(n)), dim3(256), (const TT*)dy, (const TT*)y, (TT*)dx, n, op);
   return hipGetLastError();
 }
 
 // out[0] = scale * sum(x); ws holds >= ttdk_sum_blocks(n) floats
-TTDK_EXPORT int ttdk_sum_blocks(long long n) {
+TTDK_API(int, ttdk_sum_blocks, (long long n)) {
   long long b = (n + 4095) / 4096;
   return static_cast<int>(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
 
-TTDK_EXPORT int ttdk_sum_all(const void* x, int dt, long long n, float* ws, float scale, void* out, hipStream_t st) {
+TTDK_API(int, ttdk_sum_all, (const void* x, int dt, long long n, float* ws, float scale, void* out, hipStream_t st)) {
   const int nb = ttdk_sum_blocks(n);
   TTDK_LAUNCH_DT(dt, sum_partial_kernel, dim3(nb), dim3(256), (const TT*)x, n, ws);
   TTDK_LAUNCH_DT(dt, sum_final_kernel, dim3(1), dim3(256), ws, nb, scale, (TT*)out);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_fill_scaled(void* dx, int dt, long long n, const void* g, float scale, hipStream_t st) {
+TTDK_API(int, ttdk_fill_scaled, (void* dx, int dt, long long n, const void* g, float scale, hipStream_t st)) {
   TTDK_LAUNCH_DT(dt, fill_scaled_kernel, dim3(grid_for(n)), dim3(256), (TT*)dx, n, (const TT*)g, scale);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_row_scale(const void* a, const float* g, void* out, int dt, long long rows, int C, hipStream_t st) {
+TTDK_API(int, ttdk_row_scale, (const void* a, const float* g, void* out, int dt, long long rows, int C, hipStream_t st)) {
   const long long n = rows * C;
   TTDK_LAUNCH_DT(dt, row_scale_kernel, dim3(grid_for(n)), dim3(256), (const TT*)a, g, (TT*)out, n, C);
   return hipGetLastError();
 }
 
 // zero a device buffer on the stream (the runtime's fill, not a framework elementwise kernel)
-TTDK_EXPORT int ttdk_zero(void* p, long long bytes, hipStream_t st) { return hipMemsetAsync(p, 0, bytes, st); }
+TTDK_API(int, ttdk_zero, (void* p, long long bytes, hipStream_t st)) { return hipMemsetAsync(p, 0, bytes, st); }
 // Device-to-device copy on the stream (a runtime blit, capturable as a memcpy node): small
 // parameter-row gathers without a torch cat / copy kernel in the step.
-TTDK_EXPORT int ttdk_copy(void* dst, const void* src, long long bytes, hipStream_t st) {
+TTDK_API(int, ttdk_copy, (void* dst, const void* src, long long bytes, hipStream_t st)) {
   return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
 }
 
-TTDK_EXPORT int ttdk_trace_marker(int tag, hipStream_t st) {
+TTDK_API(int, ttdk_trace_marker, (int tag, hipStream_t st)) {
   hipLaunchKernelGGL(trace_marker_kernel, dim3(1), dim3(64), 0, st, tag);
   return hipGetLastError();
 }

@@ -338,25 +338,25 @@ __global__ void lr_schedule_kernel(long long* __restrict__ step, const float* __
 
 using namespace ttdk;
 
-TTDK_EXPORT int ttdk_opt_sgd(float* w, const float* g, float* mom, bf16_t* wbf, const void* chunks, int n_chunks,
-                             const float* seg_wd, const float* hyper, const float* sumsq, int kind, hipStream_t st) {
+TTDK_API(int, ttdk_opt_sgd, (float* w, const float* g, float* mom, bf16_t* wbf, const void* chunks, int n_chunks,
+                             const float* seg_wd, const float* hyper, const float* sumsq, int kind, hipStream_t st)) {
   hipLaunchKernelGGL(sgd_kernel, dim3(n_chunks), dim3(256), 0, st, w, g, mom, wbf, static_cast<const Chunk*>(chunks),
                      seg_wd, hyper, sumsq, kind);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_opt_adam(float* w, const float* g, float* m, float* v, bf16_t* wbf, const void* chunks,
+TTDK_API(int, ttdk_opt_adam, (float* w, const float* g, float* m, float* v, bf16_t* wbf, const void* chunks,
                               int n_chunks, const float* seg_wd, const float* hyper, const float* sumsq, int decoupled,
-                              hipStream_t st) {
+                              hipStream_t st)) {
   hipLaunchKernelGGL(adam_kernel, dim3(n_chunks), dim3(256), 0, st, w, g, m, v, wbf, static_cast<const Chunk*>(chunks),
                      seg_wd, hyper, sumsq, decoupled);
   return hipGetLastError();
 }
 
 // u: scratch of the flat size; seg_norms: fp32[2*n_segments]; chunk_norms: fp32[2*n_chunks].
-TTDK_EXPORT int ttdk_opt_lamb(float* w, const float* g, float* m, float* v, float* u, bf16_t* wbf, const void* chunks,
+TTDK_API(int, ttdk_opt_lamb, (float* w, const float* g, float* m, float* v, float* u, bf16_t* wbf, const void* chunks,
                               int n_chunks, int n_segments, const float* seg_wd, const float* hyper, const float* sumsq,
-                              float* seg_norms, float* chunk_norms, hipStream_t st) {
+                              float* seg_norms, float* chunk_norms, hipStream_t st)) {
   if (!chunk_norms) return hipErrorInvalidValue;
   const Chunk* c = static_cast<const Chunk*>(chunks);
   hipLaunchKernelGGL(lamb_phase1_kernel, dim3(n_chunks), dim3(256), 0, st, w, g, m, v, u, c, seg_wd, hyper, sumsq,
@@ -367,7 +367,7 @@ TTDK_EXPORT int ttdk_opt_lamb(float* w, const float* g, float* m, float* v, floa
 }
 
 // out (fp32 scalar) = sum x^2; `partial`: scratch of >= 2048 floats.
-TTDK_EXPORT int ttdk_sumsq(const float* x, long long n, float* out, float* partial, hipStream_t st) {
+TTDK_API(int, ttdk_sumsq, (const float* x, long long n, float* out, float* partial, hipStream_t st)) {
   if (!partial) return hipErrorInvalidValue;
   long long blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
@@ -379,8 +379,8 @@ TTDK_EXPORT int ttdk_sumsq(const float* x, long long n, float* out, float* parti
 
 // out (fp32 scalar) = sum x^2 over the elements the chunk table covers; `partial`: scratch of
 // >= n_chunks floats.
-TTDK_EXPORT int ttdk_sumsq_chunks(const float* x, const void* chunks, int n_chunks, float* out, float* partial,
-                                  hipStream_t st) {
+TTDK_API(int, ttdk_sumsq_chunks, (const float* x, const void* chunks, int n_chunks, float* out, float* partial,
+                                  hipStream_t st)) {
   if (!partial || n_chunks < 0) return hipErrorInvalidValue;
   if (n_chunks > 0)
     hipLaunchKernelGGL(sumsq_chunks_kernel, dim3(n_chunks), dim3(256), 0, st, x, static_cast<const Chunk*>(chunks),
@@ -389,8 +389,8 @@ TTDK_EXPORT int ttdk_sumsq_chunks(const float* x, const void* chunks, int n_chun
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_lr_schedule(long long* step, const float* sched, int kind, float* hyper, float beta1, float beta2,
-                                 int increment, hipStream_t st) {
+TTDK_API(int, ttdk_lr_schedule, (long long* step, const float* sched, int kind, float* hyper, float beta1, float beta2,
+                                 int increment, hipStream_t st)) {
   hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(64), 0, st, step, sched, kind, hyper, beta1, beta2, increment);
   return hipGetLastError();
 }

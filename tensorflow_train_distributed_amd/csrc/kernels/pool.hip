@@ -334,8 +334,8 @@ inline int grid_for(long long n) {
 
 using namespace ttdk;
 
-TTDK_EXPORT int ttdk_maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* arg, int N, int H, int W, int C, int P, int Q,
-                                 int R, int S, int sh, int sw, int ph, int pw, hipStream_t st) {
+TTDK_API(int, ttdk_maxpool_fwd, (const bf16_t* x, bf16_t* y, uint8_t* arg, int N, int H, int W, int C, int P, int Q,
+                                 int R, int S, int sh, int sw, int ph, int pw, hipStream_t st)) {
   if (C % 8 || R * S > 255) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(N) * P * Q * (C / 8);
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, x, y, arg, N, H, W, C, P, Q, R, S,
@@ -343,8 +343,8 @@ TTDK_EXPORT int ttdk_maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* arg, int N
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_maxpool_bwd(const bf16_t* dy, const uint8_t* arg, bf16_t* dx, int N, int H, int W, int C, int P,
-                                 int Q, int R, int S, int sh, int sw, int ph, int pw, hipStream_t st) {
+TTDK_API(int, ttdk_maxpool_bwd, (const bf16_t* dy, const uint8_t* arg, bf16_t* dx, int N, int H, int W, int C, int P,
+                                 int Q, int R, int S, int sh, int sw, int ph, int pw, hipStream_t st)) {
   if (C % 8) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(N) * H * W * (C / 8);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, dy, arg, dx, N, H, W, C, P, Q, R, S,
@@ -352,14 +352,14 @@ TTDK_EXPORT int ttdk_maxpool_bwd(const bf16_t* dy, const uint8_t* arg, bf16_t* d
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_avgpool_fwd(const bf16_t* x, bf16_t* y, float* yf, int N, int HW, int C, hipStream_t st) {
+TTDK_API(int, ttdk_avgpool_fwd, (const bf16_t* x, bf16_t* y, float* yf, int N, int HW, int C, hipStream_t st)) {
   if (C % 8) return hipErrorInvalidValue;
   const int cg = C / 8;
   hipLaunchKernelGGL(avgpool_fwd_kernel, dim3((cg + 63) / 64, N), dim3(64), 0, st, x, y, yf, HW, C);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_avgpool_bwd(const bf16_t* dy, bf16_t* dx, int N, int HW, int C, hipStream_t st) {
+TTDK_API(int, ttdk_avgpool_bwd, (const bf16_t* dy, bf16_t* dx, int N, int HW, int C, hipStream_t st)) {
   if (C % 8) return hipErrorInvalidValue;
   const long long total8 = static_cast<long long>(N) * HW * (C / 8);
   hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for(total8)), dim3(256), 0, st, dy, dx, total8, HW, C);
@@ -372,9 +372,9 @@ static bool stem_pool_ok(int N, int H, int W, int C, int P, int Q) {
 }
 
 // Fused BN-apply + ReLU + 3x3/s2/p1 max pooling (ResNet stem): see bn_relu_maxpool_kernel.
-TTDK_EXPORT int ttdk_bn_relu_maxpool(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
+TTDK_API(int, ttdk_bn_relu_maxpool, (const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
                                      uint8_t* arg, uint8_t* mask, int N, int H, int W, int C, int P, int Q,
-                                     hipStream_t st) {
+                                     hipStream_t st)) {
   if (!stem_pool_ok(N, H, W, C, P, Q)) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(N) * P * Q * (C / 8);
   hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, st, y, scale, shift, out, arg, mask,
@@ -383,16 +383,16 @@ TTDK_EXPORT int ttdk_bn_relu_maxpool(const bf16_t* y, const float* scale, const 
 }
 
 // Rows of `partial` ttdk_maxpool_bwd_bnstat writes (its grid size).
-TTDK_EXPORT int ttdk_maxpool_bwd_bnstat_blocks(int N, int P, int Q, int C) {
+TTDK_API(int, ttdk_maxpool_bwd_bnstat_blocks, (int N, int P, int Q, int C)) {
   const long long per_block = 256 / (C / 8);
   long long b = (static_cast<long long>(N) * P * Q + per_block * 4 - 1) / (per_block * 4);  // ~4 blocks per thread
   return static_cast<int>(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
 // Fused max-pool backward + ReLU mask + BN-backward partial sums (see maxpool_bwd_bnstat_kernel).
-TTDK_EXPORT int ttdk_maxpool_bwd_bnstat(const bf16_t* dy, const uint8_t* arg, const uint8_t* mask, const bf16_t* y,
+TTDK_API(int, ttdk_maxpool_bwd_bnstat, (const bf16_t* dy, const uint8_t* arg, const uint8_t* mask, const bf16_t* y,
                                         bf16_t* g, float* partial, int N, int H, int W, int C, int P, int Q,
-                                        hipStream_t st) {
+                                        hipStream_t st)) {
   if (!stem_pool_ok(N, H, W, C, P, Q)) return hipErrorInvalidValue;
   const int grid = ttdk_maxpool_bwd_bnstat_blocks(N, P, Q, C);
   hipLaunchKernelGGL(maxpool_bwd_bnstat_kernel, dim3(grid), dim3(256), 0, st, dy, arg, mask, y, g, partial, N, H, W,

@@ -609,11 +609,11 @@ using namespace ttdk;
 
 // Rows per output tile (the BN partial-statistics row count is ceil(M / rows)) of ttdk_pw_conv
 // for an N x K pointwise conv, or 0 when the shape is not handled by the streaming kernel.
-TTDK_EXPORT int ttdk_pw_rows(int N, int K, int dma) { return pw::pick(N, K, dma != 0).bm; }
+TTDK_API(int, ttdk_pw_rows, (int N, int K, int dma)) { return pw::pick(N, K, dma != 0).bm; }
 
 // Workgroups (= weight-gradient slabs) of ttdk_pw_conv_wgrad for this shape; 0 = not fusable.
 // max_wgs > 0 caps the persistent grid (a launch on the side stream must not hold every CU).
-TTDK_EXPORT int ttdk_pw_wgrad_slabs(int M, int N, int K, int dma, int max_wgs) {
+TTDK_API(int, ttdk_pw_wgrad_slabs, (int M, int N, int K, int dma, int max_wgs)) {
   const pw::Cfg c = pw::pick(N, K, dma != 0);
   const bool shape = (K * N == 16384 && N % 64 == 0) || (K == 64 && N == 64);
   if (c.bm == 0 || c.bn != N || K % 32 || !shape) return 0;
@@ -624,10 +624,10 @@ TTDK_EXPORT int ttdk_pw_wgrad_slabs(int M, int N, int K, int dma, int max_wgs) {
 // x, x2: [M][K] bf16 (row stride K); mask_in: bits of x (pro 2); s/b/rs/rb: BN coefficients
 // (pro 1: scale, shift, residual scale/shift; pro 2: s = coef[3][K]); side/side_mask: where the
 // prologue stores A' (and its ReLU bits). The epilogue descriptor is the GEMM engine's.
-TTDK_EXPORT int ttdk_pw_conv(const bf16_t* x, const bf16_t* x2, const uint8_t* mask_in, const float* s, const float* b,
+TTDK_API(int, ttdk_pw_conv, (const bf16_t* x, const bf16_t* x2, const uint8_t* mask_in, const float* s, const float* b,
                              const float* rs, const float* rb, bf16_t* side, uint8_t* side_mask, int relu, int pro,
                              const bf16_t* w, long long ldw, int M, int N, int K, const TtdkEpilogue* epi,
-                             hipStream_t st) {
+                             hipStream_t st)) {
   const EpiParams e0 = to_epi(epi);
   // the LDS-DMA epilogue serves the accumulate / BN-statistics inputs (no residual, no second source)
   const bool dma = (e0.beta || e0.by) && !e0.residual && !e0.by2 && e0.act == 0 && !e0.bias;
@@ -653,10 +653,10 @@ TTDK_EXPORT int ttdk_pw_conv(const bf16_t* x, const bf16_t* x2, const uint8_t* m
 // beta_w) = dz^T . xw with dz never stored; ws: ttdk_pw_wgrad_slabs(M, N, K, dma, max_wgs) * K * N
 // floats. dw == null: the slabs are left in ws for the caller to fold (ttdk_splitk_reduce), e.g. on
 // the weight-gradient side stream so the data-gradient chain does not wait for the fold.
-TTDK_EXPORT int ttdk_pw_conv_wgrad(const bf16_t* g, const bf16_t* y, const uint8_t* mask_in, const float* coef,
+TTDK_API(int, ttdk_pw_conv_wgrad, (const bf16_t* g, const bf16_t* y, const uint8_t* mask_in, const float* coef,
                                    const bf16_t* xw, const bf16_t* w, long long ldw, int M, int N, int K,
                                    const TtdkEpilogue* epi, float* dw, float* ws, int beta_w, int max_wgs,
-                                   hipStream_t st) {
+                                   hipStream_t st)) {
   const EpiParams e = to_epi(epi);
   const bool dma = (e.beta || e.by) && !e.residual && !e.by2 && e.act == 0 && !e.bias;
   const int slabs = ttdk_pw_wgrad_slabs(M, N, K, dma, max_wgs);

@@ -34,8 +34,8 @@
 #include "tile_common.h"
 
 // transformer.hip
-TTDK_EXPORT int ttdk_colreduce(const float* part, int nb, int C, int stride, float* out, int beta, hipStream_t st);
-TTDK_EXPORT int ttdk_ln_bwd_num_blocks(int rows);
+extern "C" int ttdk_colreduce(const float* part, int nb, int C, int stride, float* out, int beta, hipStream_t st);
+extern "C" int ttdk_ln_bwd_num_blocks(int rows);
 
 namespace ttdk {
 namespace {
@@ -547,9 +547,9 @@ static bool rms_width_ok(int H) { return H == 512 || H == 1024 || H == 1536 || H
 
 // x, res (nullable), s_out (nullable), y: bf16 [rows, H] dense, 16-byte aligned; rstd fp32 [rows];
 // gamma fp32 [H], 16-byte aligned. Bad arguments return hipErrorInvalidValue without a launch.
-TTDK_EXPORT int ttdk_rms_fwd(const bf16_t* x, const bf16_t* res, bf16_t* s_out, bf16_t* y, float* rstd,
+TTDK_API(int, ttdk_rms_fwd, (const bf16_t* x, const bf16_t* res, bf16_t* s_out, bf16_t* y, float* rstd,
                              const float* gamma, int rows, int H, float eps, float p_in, unsigned site_in, float p_out,
-                             unsigned site_out, const long long* rng, hipStream_t st) {
+                             unsigned site_out, const long long* rng, hipStream_t st)) {
   if (!rms_width_ok(H) || rows < 0 || !x || !y || !rstd || !gamma) return hipErrorInvalidValue;
   if (!aligned16(x) || !aligned16(res) || !aligned16(s_out) || !aligned16(y) || !aligned16(gamma))
     return hipErrorInvalidValue;
@@ -562,12 +562,12 @@ TTDK_EXPORT int ttdk_rms_fwd(const bf16_t* x, const bf16_t* res, bf16_t* s_out, 
 }
 
 // Blocks of rms_bwd_kernel (= partial rows of the workspace): LayerNorm's count.
-TTDK_EXPORT int ttdk_rms_bwd_num_blocks(int rows) { return ttdk_ln_bwd_num_blocks(rows); }
+TTDK_API(int, ttdk_rms_bwd_num_blocks, (int rows)) { return ttdk_ln_bwd_num_blocks(rows); }
 
 // part: fp32 [ttdk_rms_bwd_num_blocks(rows)][H] workspace; dgamma written (accumulate = 0) or added to.
-TTDK_EXPORT int ttdk_rms_bwd(const bf16_t* dy, const bf16_t* s, const float* rstd, const float* gamma, bf16_t* ds_out,
+TTDK_API(int, ttdk_rms_bwd, (const bf16_t* dy, const bf16_t* s, const float* rstd, const float* gamma, bf16_t* ds_out,
                              bf16_t* dx_out, float* part, float* dgamma, int accumulate, int rows, int H, float p_in,
-                             unsigned site_in, float p_out, unsigned site_out, const long long* rng, hipStream_t st) {
+                             unsigned site_in, float p_out, unsigned site_out, const long long* rng, hipStream_t st)) {
   if (!rms_width_ok(H) || rows <= 0 || !dy || !s || !rstd || !gamma || !ds_out || !part || !dgamma)
     return hipErrorInvalidValue;
   if (!aligned16(dy) || !aligned16(s) || !aligned16(gamma) || !aligned16(ds_out) || !aligned16(dx_out) ||
@@ -581,8 +581,8 @@ TTDK_EXPORT int ttdk_rms_bwd(const bf16_t* dy, const bf16_t* s, const float* rst
   return ttdk_colreduce(part, nb, H, H, dgamma, accumulate, st);
 }
 
-TTDK_EXPORT int ttdk_rms_generic_fwd(const void* x, const float* g, void* y, float* rstd, int dt, long long rows, int H,
-                                     float eps, hipStream_t st) {
+TTDK_API(int, ttdk_rms_generic_fwd, (const void* x, const float* g, void* y, float* rstd, int dt, long long rows, int H,
+                                     float eps, hipStream_t st)) {
   if (H <= 0 || rows <= 0 || !x || !g || !y || !rstd) return hipErrorInvalidValue;
   dim3 grid(static_cast<unsigned>((rows + 3) / 4));
   if (dt == 0)
@@ -597,7 +597,7 @@ TTDK_EXPORT int ttdk_rms_generic_fwd(const void* x, const float* g, void* y, flo
 }
 
 // Row blocks the generic dgamma kernel splits the rows into (= rows of its [T][H] workspace).
-TTDK_EXPORT int ttdk_rms_generic_parts(long long rows, int H) {
+TTDK_API(int, ttdk_rms_generic_parts, (long long rows, int H)) {
   const long long cb = (H + 63) / 64;
   long long t = (rows + 255) / 256;
   const long long cap = 2048 / cb > 1 ? 2048 / cb : 1;
@@ -607,9 +607,9 @@ TTDK_EXPORT int ttdk_rms_generic_parts(long long rows, int H) {
 
 // dx (nullable: not wanted) and dgamma (fp32 [H], written or added to); part: fp32
 // [ttdk_rms_generic_parts(rows, H)][H] workspace.
-TTDK_EXPORT int ttdk_rms_generic_bwd(const void* dy, const void* x, const float* g, const float* rstd, void* dx,
+TTDK_API(int, ttdk_rms_generic_bwd, (const void* dy, const void* x, const float* g, const float* rstd, void* dx,
                                      float* part, float* dgamma, int accumulate, int dt, long long rows, int H,
-                                     hipStream_t st) {
+                                     hipStream_t st)) {
   if (H <= 0 || rows <= 0 || !dy || !x || !g || !rstd || !part || !dgamma || (dt != 0 && dt != 1))
     return hipErrorInvalidValue;
   const int T = ttdk_rms_generic_parts(rows, H);
@@ -633,7 +633,7 @@ TTDK_EXPORT int ttdk_rms_generic_bwd(const void* dy, const void* x, const float*
 }
 
 // Number of threads the capped SwiGLU grid launches (tests size their grid-stride case from it).
-TTDK_EXPORT int ttdk_swiglu_max_threads() { return kGluMaxBlocks * kGluBlock; }
+TTDK_API(int, ttdk_swiglu_max_threads, ()) { return kGluMaxBlocks * kGluBlock; }
 
 static bool glu_vec_ok(int dt, int I, long long ld0, long long ld1, long long ld2, const void* p0, const void* p1,
                        const void* p2) {
@@ -643,8 +643,8 @@ static bool glu_vec_ok(int dt, int I, long long ld0, long long ld1, long long ld
 
 // h[r, :I] = silu(x2[r, :I]) * x2[r, I:2I]. x2: [rows, >= 2I] with row stride ldx, h: [rows, >= I]
 // with row stride ldh (elements), both of type dt and element-aligned. x2 and h must not overlap.
-TTDK_EXPORT int ttdk_swiglu_fwd(const void* x2, long long ldx, void* h, long long ldh, int dt, long long rows, int I,
-                                hipStream_t st) {
+TTDK_API(int, ttdk_swiglu_fwd, (const void* x2, long long ldx, void* h, long long ldh, int dt, long long rows, int I,
+                                hipStream_t st)) {
   if ((dt != 0 && dt != 1) || rows < 0 || I <= 0 || !x2 || !h) return hipErrorInvalidValue;
   if (ldx < 2LL * I || ldh < I || rows > (1LL << 40)) return hipErrorInvalidValue;
   const uintptr_t em = dt == 0 ? 3 : 1;
@@ -657,8 +657,8 @@ TTDK_EXPORT int ttdk_swiglu_fwd(const void* x2, long long ldx, void* h, long lon
 
 // dx2[r] = [da | db] from dh [rows, >= I] (row stride ldh) and x2 [rows, >= 2I] (ldx); dx2 [rows, >= 2I]
 // (ldd). dx2 == x2 with ldd == ldx is in place; any other overlap is the caller's error.
-TTDK_EXPORT int ttdk_swiglu_bwd(const void* dh, long long ldh, const void* x2, long long ldx, void* dx2, long long ldd,
-                                int dt, long long rows, int I, hipStream_t st) {
+TTDK_API(int, ttdk_swiglu_bwd, (const void* dh, long long ldh, const void* x2, long long ldx, void* dx2, long long ldd,
+                                int dt, long long rows, int I, hipStream_t st)) {
   if ((dt != 0 && dt != 1) || rows < 0 || I <= 0 || !dh || !x2 || !dx2) return hipErrorInvalidValue;
   if (ldh < I || ldx < 2LL * I || ldd < 2LL * I || rows > (1LL << 40)) return hipErrorInvalidValue;
   if (dx2 == x2 && ldd != ldx) return hipErrorInvalidValue;

@@ -145,15 +145,15 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 using namespace ttdk;
 
 // Number of threads the capped grid launches (tests size their grid-stride case from it).
-TTDK_EXPORT int ttdk_rope_max_threads() { return kRopeMaxBlocks * kRopeBlock; }
+TTDK_API(int, ttdk_rope_max_threads, ()) { return kRopeMaxBlocks * kRopeBlock; }
 
 // y[r, :heads*64] = rotation of x[r, :heads*64] at position pos0 + r % S (inverse != 0: the inverse
 // rotation). x, y: [tokens, >= heads*64], row strides ldx / ldy in elements, type dt (0 fp32, 1 bf16);
 // table fp32 [table_rows][2][32]. y == x with ldy == ldx is in place; any other overlap is the
 // caller's error (not checked). Bad arguments return hipErrorInvalidValue without a launch;
 // tokens == 0 returns 0 without a launch.
-TTDK_EXPORT int ttdk_rope(const void* x, long long ldx, void* y, long long ldy, int dt, const float* table,
-                          int table_rows, long long tokens, int S, int heads, int pos0, int inverse, hipStream_t st) {
+TTDK_API(int, ttdk_rope, (const void* x, long long ldx, void* y, long long ldy, int dt, const float* table,
+                          int table_rows, long long tokens, int S, int heads, int pos0, int inverse, hipStream_t st)) {
   if (heads <= 0 || heads > (1 << 20) || S <= 0 || tokens < 0) return hipErrorInvalidValue;
   if (tokens % S != 0) return hipErrorInvalidValue;
   if (pos0 < 0 || static_cast<long long>(pos0) + S > table_rows) return hipErrorInvalidValue;

@@ -239,15 +239,15 @@ __global__ __launch_bounds__(THR, 1) void stem_fwd_kernel(const bf16_t* __restri
 using namespace ttdk;
 
 // Workgroups (= BN partial-sum rows) of ttdk_stem_fwd for a batch of N images.
-TTDK_EXPORT int ttdk_stem_fwd_blocks(int N) {
+TTDK_API(int, ttdk_stem_fwd_blocks, (int N)) {
   const int per = (N + 255) / 256;
   return (N + per - 1) / per;
 }
 
 // x [N][224][224][cin] bf16 (cin = 3, or 8 with channels 3..7 zero), w [64][7][7][8] bf16 ->
 // y [N][112][112][64] bf16, part [blocks][2][64] fp32 (per-workgroup sum / sum of squares of y).
-TTDK_EXPORT int ttdk_stem_fwd(const bf16_t* x, const bf16_t* w, bf16_t* y, float* part, int N, int H, int Wd, int cin,
-                              hipStream_t st) {
+TTDK_API(int, ttdk_stem_fwd, (const bf16_t* x, const bf16_t* w, bf16_t* y, float* part, int N, int H, int Wd, int cin,
+                              hipStream_t st)) {
   if (cin != 3 && cin != 8) return hipErrorInvalidValue;
   if (N <= 0 || H != stemf::W || Wd != stemf::W) return hipErrorInvalidValue;
   const int P = (H + 6 - 7) / 2 + 1;

@@ -204,15 +204,15 @@ __global__ void stem_scatter_kernel(const float* __restrict__ sums, float* __res
 using namespace ttdk;
 
 // Workgroups of ttdk_stem_wgrad (the caller's workspace holds workgroups*64*160 + 64*160 floats).
-TTDK_EXPORT int ttdk_stem_wgrad_blocks(int N, int P, int Q) {
+TTDK_API(int, ttdk_stem_wgrad_blocks, (int N, int P, int Q)) {
   const long long units = static_cast<long long>(N) * ((P + stem::BAND - 1) / stem::BAND) * ((Q + stem::QB - 1) / stem::QB);
   const int want = 3 * 256;
   return static_cast<int>(units < want ? units : want);
 }
 
 // x [N][H][W][cin] (cin = 3, or 8 with 3 real channels), g / y [N][P][Q][64], coef [3][64] -> dw [64][7][7][8] fp32.
-TTDK_EXPORT int ttdk_stem_wgrad(const bf16_t* x, const bf16_t* g, const bf16_t* y, const float* coef, float* dw,
-                                float* ws, int N, int H, int W, int P, int Q, int beta, int cin, hipStream_t st) {
+TTDK_API(int, ttdk_stem_wgrad, (const bf16_t* x, const bf16_t* g, const bf16_t* y, const float* coef, float* dw,
+                                float* ws, int N, int H, int W, int P, int Q, int beta, int cin, hipStream_t st)) {
   if (cin != 3 && cin != 8) return hipErrorInvalidValue;
   if (P != (H + 6 - 7) / 2 + 1 || Q != (W + 6 - 7) / 2 + 1 || N <= 0) return hipErrorInvalidValue;
   const int units = N * ((P + stem::BAND - 1) / stem::BAND) * ((Q + stem::QB - 1) / stem::QB);

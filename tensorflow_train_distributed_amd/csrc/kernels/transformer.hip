@@ -643,9 +643,9 @@ inline bool ln_bwd_prefetch() {
     default: return hipErrorInvalidValue;                                                \
   }
 
-TTDK_EXPORT int ttdk_ln_fwd(const bf16_t* x, const bf16_t* res, bf16_t* s_out, bf16_t* y, float* mean, float* rstd,
+TTDK_API(int, ttdk_ln_fwd, (const bf16_t* x, const bf16_t* res, bf16_t* s_out, bf16_t* y, float* mean, float* rstd,
                             const float* gamma, const float* beta, int rows, int H, float eps, float p_in,
-                            unsigned site_in, float p_out, unsigned site_out, const long long* rng, hipStream_t st) {
+                            unsigned site_in, float p_out, unsigned site_out, const long long* rng, hipStream_t st)) {
   if ((p_in > 0.f || p_out > 0.f) && !rng) return hipErrorInvalidValue;
   DropSpec d = make_drop(rng, site_in, p_in, site_out, p_out);
   dim3 grid((rows + 3) / 4), block(256);
@@ -656,7 +656,7 @@ TTDK_EXPORT int ttdk_ln_fwd(const bf16_t* x, const bf16_t* res, bf16_t* s_out, b
 // Blocks of ln_bwd_kernel (= partial rows of the workspace): one 8-wave block per CU. Two per CU
 // (4 waves per SIMD at the H = 1024 kernel's 120 VGPRs) measured the same standalone (146 vs 147
 // us at 65536 x 1024) and in the BERT step, four slower (TTD_LN_BWD_BLOCKS: A/B).
-TTDK_EXPORT int ttdk_ln_bwd_num_blocks(int rows) {
+TTDK_API(int, ttdk_ln_bwd_num_blocks, (int rows)) {
   static const int cap = [] {
     const char* e = getenv("TTD_LN_BWD_BLOCKS");
     const int v = e ? atoi(e) : 256;
@@ -666,10 +666,10 @@ TTDK_EXPORT int ttdk_ln_bwd_num_blocks(int rows) {
 }
 
 // part: fp32 [nblocks][2][H] workspace; dgamma/dbeta written (beta=0) or accumulated.
-TTDK_EXPORT int ttdk_ln_bwd(const bf16_t* dy, const bf16_t* s, const float* mean, const float* rstd,
+TTDK_API(int, ttdk_ln_bwd, (const bf16_t* dy, const bf16_t* s, const float* mean, const float* rstd,
                             const float* gamma, bf16_t* ds_out, bf16_t* dx_out, float* part, float* dgamma,
                             float* dbeta, int accumulate, int rows, int H, float p_in, unsigned site_in, float p_out,
-                            unsigned site_out, const long long* rng, hipStream_t st) {
+                            unsigned site_out, const long long* rng, hipStream_t st)) {
   if ((p_in > 0.f || p_out > 0.f) && !rng) return hipErrorInvalidValue;
   DropSpec d = make_drop(rng, site_in, p_in, site_out, p_out);
   const int nb = ttdk_ln_bwd_num_blocks(rows);
@@ -688,15 +688,15 @@ TTDK_EXPORT int ttdk_ln_bwd(const bf16_t* dy, const bf16_t* s, const float* mean
 }
 
 // out[c] (+)= sum_b part[b * stride + c], c < C.
-TTDK_EXPORT int ttdk_colreduce(const float* part, int nb, int C, int stride, float* out, int beta, hipStream_t st) {
+TTDK_API(int, ttdk_colreduce, (const float* part, int nb, int C, int stride, float* out, int beta, hipStream_t st)) {
   if (C % 4 || stride % 4 || (reinterpret_cast<uintptr_t>(part) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(colreduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, part, nb, C, stride, out, beta);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_embed_fwd(const int* ids, const int* tt, const bf16_t* word, const bf16_t* pos, const bf16_t* typ,
-                               bf16_t* s, long long rows, int S, int H, hipStream_t st) {
+TTDK_API(int, ttdk_embed_fwd, (const int* ids, const int* tt, const bf16_t* word, const bf16_t* pos, const bf16_t* typ,
+                               bf16_t* s, long long rows, int S, int H, hipStream_t st)) {
   if (H % 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(embed_fwd_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, ids, tt, word, pos,
                      typ, s, rows, S, H);
@@ -704,8 +704,8 @@ TTDK_EXPORT int ttdk_embed_fwd(const int* ids, const int* tt, const bf16_t* word
 }
 
 // dword must already hold (or be zeroed for) the other contributions (e.g. the tied decoder).
-TTDK_EXPORT int ttdk_embed_bwd(const bf16_t* ds, const int* ids, const int* tt, float* dword, float* dpos, float* dtype,
-                               int B, int S, int H, int T, int pos_beta, hipStream_t st) {
+TTDK_API(int, ttdk_embed_bwd, (const bf16_t* ds, const int* ids, const int* tt, float* dword, float* dpos, float* dtype,
+                               int B, int S, int H, int T, int pos_beta, hipStream_t st)) {
   if (H % 8 || H / 8 > 256 || T > 4) return hipErrorInvalidValue;
   const long long rows = static_cast<long long>(B) * S;
   hipLaunchKernelGGL(embed_bwd_word_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, ds, ids,
@@ -723,15 +723,15 @@ TTDK_EXPORT int ttdk_embed_bwd(const bf16_t* ds, const int* ids, const int* tt, 
 }
 
 // idx (nullable) + per / gs: see gather_rows_kernel; per = 1, gs = 0 is a plain index gather.
-TTDK_EXPORT int ttdk_gather_rows(const bf16_t* src, long long ld_src, const int* idx, int per, long long gs, bf16_t* dst,
-                                 int n, int H, hipStream_t st) {
+TTDK_API(int, ttdk_gather_rows, (const bf16_t* src, long long ld_src, const int* idx, int per, long long gs, bf16_t* dst,
+                                 int n, int H, hipStream_t st)) {
   if (H % 8 || ld_src % 8 || per < 1 || (!idx && gs == 0 && n > 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, st, src, ld_src, idx, per, gs, dst, n, H);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_scatter_rows(const bf16_t* src, const int* idx, int per, long long gs, bf16_t* dst, long long ld_dst,
-                                  int n, int H, int accumulate, hipStream_t st) {
+TTDK_API(int, ttdk_scatter_rows, (const bf16_t* src, const int* idx, int per, long long gs, bf16_t* dst, long long ld_dst,
+                                  int n, int H, int accumulate, hipStream_t st)) {
   if (H % 8 || ld_dst % 8 || per < 1 || (!idx && gs == 0 && n > 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(scatter_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, st, src, idx, per, gs, dst, ld_dst, n, H,
                      accumulate);
@@ -743,40 +743,40 @@ __global__ void rng_advance_kernel(long long* __restrict__ t) {
   if (threadIdx.x == 0) t[1] = t[1] + 1;
 }
 
-TTDK_EXPORT int ttdk_rng_advance(long long* t, hipStream_t st) {
+TTDK_API(int, ttdk_rng_advance, (long long* t, hipStream_t st)) {
   hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(64), 0, st, t);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_count_valid(const int* labels, int n, float scale, float* inv_count, hipStream_t st) {
+TTDK_API(int, ttdk_count_valid, (const int* labels, int n, float scale, float* inv_count, hipStream_t st)) {
   hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(256), 0, st, labels, n, scale, inv_count, 0);
   return hipGetLastError();
 }
 
 // out[0] = 1 / count, out[1] = scale / count (count = labels >= 0)
-TTDK_EXPORT int ttdk_count_valid2(const int* labels, int n, float scale, float* out, hipStream_t st) {
+TTDK_API(int, ttdk_count_valid2, (const int* labels, int n, float scale, float* out, hipStream_t st)) {
   hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(256), 0, st, labels, n, scale, out, 1);
   return hipGetLastError();
 }
 
 // grad scale = gsc[0] (device, e.g. from ttdk_count_valid); metric scale = msc[0] (device or
 // null = 1). sums (fp32[2]) is accumulated, not zeroed.
-TTDK_EXPORT int ttdk_xent_vocab(const bf16_t* logits, long long ld, int V, const int* labels, int rows, const float* gsc,
-                                bf16_t* dlogits, float* sums, const float* msc, hipStream_t st) {
+TTDK_API(int, ttdk_xent_vocab, (const bf16_t* logits, long long ld, int V, const int* labels, int rows, const float* gsc,
+                                bf16_t* dlogits, float* sums, const float* msc, hipStream_t st)) {
   if (ld % 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(xent_vocab_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, labels, gsc, dlogits, sums, msc);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_dact_bf16(const bf16_t* dy, const bf16_t* aux, bf16_t* dx, long long n, int kind,
-                               hipStream_t st) {
+TTDK_API(int, ttdk_dact_bf16, (const bf16_t* dy, const bf16_t* aux, bf16_t* dx, long long n, int kind,
+                               hipStream_t st)) {
   if (n % 8) return hipErrorInvalidValue;
   const long long n8 = n / 8;
   hipLaunchKernelGGL(dact_kernel, dim3(static_cast<unsigned>((n8 + 255) / 256)), dim3(256), 0, st, dy, aux, dx, n8, kind);
   return hipGetLastError();
 }
 
-TTDK_EXPORT int ttdk_tanh_bf16(bf16_t* x, long long n, hipStream_t st) {
+TTDK_API(int, ttdk_tanh_bf16, (bf16_t* x, long long n, hipStream_t st)) {
   hipLaunchKernelGGL(tanh_bf16_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, x, n);
   return hipGetLastError();
 }

@@ -100,9 +100,9 @@ using namespace ttdk;
 // logits_dtype: 0 = fp32, 1 = bf16. label_dtype: 0 = int32, 1 = int64.
 // sums (optional, fp32[2]) receives mean loss and mean accuracy; `part` (fp32[2*rows], needed
 // with sums) holds the per-row terms, reduced in a fixed order (bitwise reproducible).
-TTDK_EXPORT int ttdk_sparse_xent(const void* logits, int logits_dtype, const void* labels, int label_dtype, int rows,
+TTDK_API(int, ttdk_sparse_xent, (const void* logits, int logits_dtype, const void* labels, int label_dtype, int rows,
                                  int V, float grad_scale, float* loss_rows, void* dlogits, uint8_t* correct,
-                                 float* sums, float* part, hipStream_t st) {
+                                 float* sums, float* part, hipStream_t st)) {
   if (sums && !part) return hipErrorInvalidValue;
   const float inv = 1.f / rows;
   dim3 g(rows), b(256);

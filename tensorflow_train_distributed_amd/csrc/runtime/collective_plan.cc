@@ -5,7 +5,7 @@
 #include "common.h"
 
 // out: kMaxSteps rows of 5 int64 (kind, root, send, recv, count). Returns the number of steps.
-TTD_EXPORT int ttd_collective_plan(int algo, long long count, int nranks, int rank, long long* out) {
+TTD_API(int, ttd_collective_plan, (int algo, long long count, int nranks, int rank, long long* out)) {
   ttd_coll::Step s[ttd_coll::kMaxSteps];
   const int n = ttd_coll::plan(algo, count, nranks, rank, s);
   for (int i = 0; i < n; ++i) {
@@ -18,4 +18,4 @@ TTD_EXPORT int ttd_collective_plan(int algo, long long count, int nranks, int ra
   return n;
 }
 
-TTD_EXPORT int ttd_collective_plan_max_steps() { return ttd_coll::kMaxSteps; }
+TTD_API(int, ttd_collective_plan_max_steps, ()) { return ttd_coll::kMaxSteps; }

@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#include "../kernels/abi.h"  // TTD_API: the exports Python types from the library's own table
+
 #define TTD_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace ttd {

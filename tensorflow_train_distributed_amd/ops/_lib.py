@@ -1,9 +1,16 @@
 """ctypes bindings for ``libttd_hip.so`` (the gfx950 kernel library).
 
 Every kernel launcher has the C signature ``int ttdk_*(..., hipStream_t)``; this module
-declares the argument types once and launches on PyTorch's *current* HIP stream, so the
-kernels compose with torch's stream semantics, ``torch.cuda.graphs`` capture (hipGraph) and
-the collective engine's side streams. A non-zero return (hipError_t) raises immediately.
+launches them on PyTorch's *current* HIP stream, so the kernels compose with torch's stream
+semantics, ``torch.cuda.graphs`` capture (hipGraph) and the collective engine's side streams.
+A non-zero return (hipError_t) raises immediately.
+
+Argument and return types are not written here. Each library records the signature of every
+function defined with ``TTDK_API`` / ``TTD_API`` (csrc/kernels/abi.h), computed from the C
+function's own type, and :func:`hip` / :func:`rt` set ``argtypes`` and ``restype`` of all of them
+from that table when the library is loaded. To add an export, write it with ``TTDK_API`` and
+call it: that is all. A name the table lacks, a letter this module does not know, a wrong
+number of arguments or a struct whose layout differs from its mirror below raises.
 
 There is deliberately no fallback here: a GPU op whose kernel library is missing or fails
 to load raises (the CPU path of each op lives in :mod:`.reference`).
@@ -11,21 +18,15 @@ to load raises (the CPU path of each op lives in :mod:`.reference`).
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_float, c_int, c_longlong, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_uint, c_uint64, c_void_p
 
 import torch
 
 from .. import _native
 
-P = c_void_p
-I = c_int
-L = c_longlong
-F = c_float
-U64 = c_uint64
-
 
 class Epilogue(ctypes.Structure):
-    """Mirror of ``TtdkEpilogue`` in gemm_conv.hip."""
+    """Mirror of ``TtdkEpilogue`` in gemm_conv.h."""
 
     _fields_ = [
         ("mode", c_int), ("out", c_void_p), ("ldo", c_longlong), ("slab_stride", c_longlong),
@@ -49,131 +50,115 @@ class DwConvGeom(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "H", "W", "C", "M", "R", "S", "P", "Q", "sh", "sw", "ph", "pw", "dh", "dw")]
 
 
-E = ctypes.POINTER(Epilogue)
-G = ctypes.POINTER(ConvGeom)
-DG = ctypes.POINTER(DwConvGeom)
-
-# name -> argtypes (restype is always int = hipError_t). Structs are passed by reference.
-_SIGS = {
-    # gemm_conv.hip
-    "ttdk_gemm_bf16": [P, L, I, P, L, I, I, I, I, I, I, I, E, P],
-    "ttdk_gemm_bf16_splitk": [P, L, I, P, L, I, I, I, I, I, P, P, I, F, I, I, P],
-    "ttdk_gemm_wgrad_bias": [P, L, P, L, I, I, I, I, P, P, I, F, P, P],
-    "ttdk_gemm_wgrad_bias_ws": [I, I, I, I],
-    "ttdk_gemm4t_wgrad": [P, L, P, L, I, I, I, I, P, P, I, F, P, P],
-    "ttdk_gemm4t_ws": [I, I, I, I],
-    "ttdk_conv_fwd": [P, P, G, I, I, E, P],
-    "ttdk_conv_fwd4w": [P, P, G, E, P],
-    "ttdk_conv_dgrad4w": [P, P, G, E, P],
-    "ttdk_conv_dgrad": [P, P, G, I, I, E, P],
-    "ttdk_conv_dgrad_bnpro": [P, P, G, P, P, P, E, P],
-    "ttdk_set_inkernel_fold": [I],
-    "ttdk_conv_fwd_bnpro": [P, P, G, P, P, I, P, P, E, P],
-    "ttdk_conv_dgrad_subpixel": [P, P, G, P, I, E, P],
-    "ttdk_conv_wgrad": [P, P, G, P, P, I, I, I, I, P],
-    "ttdk_conv_wgrad4t": [P, P, G, P, P, I, I, P],
-    "ttdk_conv_wgrad4t_ws": [G, I],
-    "ttdk_conv_wgrad_bn": [P, P, P, P, G, P, P, I, I, I, I, P],
-    "ttdk_conv_wgrad_fp8": [P, P, G, P, P, I, I, P, P, P],
-    "ttdk_conv_wgrad4t8": [P, P, G, P, P, I, I, P, P, P],
-    "ttdk_conv_fwd4k8": [P, P, G, P, P, P, P, P],
-    "ttdk_conv_dgrad4k8": [P, P, G, P, P, P, P, I, P, P, P],
-    "ttdk_conv_wgrad4t8_ws": [G, I],
-    "ttdk_splitk_reduce": [P, I, L, P, I, P],
-    "ttdk_set_big_pers": [I],
-    # gemm_f32.hip
-    "ttdk_gemm_f32": [P, L, I, P, L, I, P, L, P, I, I, I, I, P],
-    # stem_fwd.hip / stem_wgrad.hip
-    "ttdk_stem_fwd_blocks": [I],
-    "ttdk_stem_fwd": [P, P, P, P, I, I, I, I, P],
-    "ttdk_stem_wgrad_blocks": [I, I, I],
-    "ttdk_stem_wgrad": [P, P, P, P, P, P, I, I, I, I, I, I, I, P],
-    # conv3_halo.hip
-    "ttdk_conv3_rows": [I, I, I, I, I],
-    "ttdk_conv3_halo": [P, P, P, P, P, P, P, I, I, P, I, I, I, I, I, E, P],
-    # pw_gemm.hip
-    "ttdk_pw_rows": [I, I, I],
-    "ttdk_pw_conv": [P, P, P, P, P, P, P, P, P, I, I, P, L, I, I, I, E, P],
-    "ttdk_pw_wgrad_slabs": [I, I, I, I, I],
-    "ttdk_pw_conv_wgrad": [P, P, P, P, P, P, L, I, I, I, E, P, P, I, I, P],
-    # batchnorm.hip
-    "ttdk_bn_num_partials": [L, I],
-    "ttdk_bn_stats_partial": [P, L, I, P, I, P],
-    "ttdk_bn_bwd_partial": [P, P, P, P, L, I, P, I, P, P],
-    "ttdk_bn_reduce_partials": [P, I, I, P, P],
-    "ttdk_bn_fwd_finalize": [P, F, I, P, P, F, F, P, P, P, P, P, P, P],
-    "ttdk_bn_finalize_slices": [I],
-    "ttdk_bn_reduce_finalize": [P, I, I, P, I, F, P, P, F, F, P, P, P, P, P, P, P, P, P, I, P],
-    "ttdk_bn_bwd_finalize": [P, F, I, P, P, P, P, P, P, I, P],
-    "ttdk_bn_apply": [P, P, P, P, P, P, P, P, P, P, L, I, I, P],
-    "ttdk_bn_bwd_apply": [P, P, P, P, P, P, L, I, P],
-    "ttdk_bn_bwd_apply_q8": [P, P, P, P, P, P, P, P, L, I, P],
-    # pool.hip
-    "ttdk_maxpool_fwd": [P, P, P] + [I] * 12 + [P],
-    "ttdk_maxpool_bwd": [P, P, P] + [I] * 12 + [P],
-    "ttdk_avgpool_fwd": [P, P, P, I, I, I, P],
-    "ttdk_bn_relu_maxpool": [P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "ttdk_maxpool_bwd_bnstat_blocks": [I, I, I, I],
-    "ttdk_maxpool_bwd_bnstat": [P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "ttdk_avgpool_bwd": [P, P, I, I, I, P],
-    # xent.hip
-    "ttdk_sparse_xent": [P, I, P, I, I, I, F, P, P, P, P, P, P],
-    # optim.hip
-    "ttdk_opt_sgd": [P, P, P, P, P, I, P, P, P, I, P],
-    "ttdk_opt_adam": [P, P, P, P, P, P, I, P, P, P, I, P],
-    "ttdk_opt_lamb": [P, P, P, P, P, P, P, I, I, P, P, P, P, P, P],
-    "ttdk_sumsq": [P, L, P, P, P],
-    "ttdk_sumsq_chunks": [P, P, I, P, P, P],
-    "ttdk_lr_schedule": [P, P, I, P, F, F, I, P],
-    # elementwise.hip
-    "ttdk_f32_to_bf16": [P, P, L, P],
-    "ttdk_bf16_to_f32": [P, P, L, P],
-    "ttdk_bf16_round_probe": [P, P, P, P, L, P],
-    "ttdk_pad_channels": [P, P, L, I, I, P],
-    "ttdk_unpad_channels": [P, P, L, I, I, P],
-    "ttdk_transpose_aca_bf16": [P, P, I, I, I, P],
-    "ttdk_transpose128_batch_bf16": [P, I, I, P],
-    "ttdk_wprep": [P, P, P, I, I, P],
-    "ttdk_transpose2d_f32": [P, P, I, I, P],
-    "ttdk_bias_act_dropout_fwd": [P, P, P, L, I, I, F, U64, U64, I, P],
-    "ttdk_bias_act_dropout_bwd": [P, P, P, P, L, I, I, F, U64, U64, I, P],
-    "ttdk_colsum": [P, L, I, P, I, I, P, P],
-    "ttdk_colsum_ws_floats": [L, I, I],
-    "ttdk_add_bf16": [P, P, P, L, F, F, P],
-    "ttdk_amax_bf16": [P, L, P, I, P],
-    "ttdk_quant_fp8": [P, P, L, P, I, P],
-    "ttdk_dequant_fp8": [P, P, L, P, I, P],
-    # fp8.hip
-    "ttdk_fp8_rollover": [P, I, F, F, P],
-    "ttdk_fp8_quant_weights": [P, P, P, I, I, P, I, P],
-}
-
-_fns = {}
+class HipKernelError(RuntimeError):
+    pass
 
 
-def register(sigs: dict):
-    _SIGS.update(sigs)
+# signature letter (abi.h) -> ctypes type; structs are passed by reference
+_STRUCTS = {"E": Epilogue, "G": ConvGeom, "D": DwConvGeom}
+_CODES = {"v": None, "i": c_int, "u": c_uint, "l": c_longlong, "Q": c_uint64, "f": c_float, "d": c_double,
+          "P": c_void_p, "z": c_char_p, **{k: ctypes.POINTER(v) for k, v in _STRUCTS.items()}}
+# the table's own two functions: the only types set by hand (and entries of the table like any other)
+_BOOT = {"_count": "i:", "_entry": "z:i"}
 
 
-_RESTYPE = {"ttdk_colsum_ws_floats": c_longlong,
-            "ttdk_gemm_wgrad_bias_ws": c_longlong, "ttdk_gemm4t_ws": c_longlong,
-            "ttdk_conv_wgrad4t_ws": c_longlong, "ttdk_conv_wgrad4t8_ws": c_longlong,
-            "ttdk_dwconv_wgrad_ws_floats": c_longlong}
+def decode(name, sig):
+    """(restype, argtypes) of signature ``ret:args``."""
+    try:
+        ret, args = sig.split(":")
+        return _CODES[ret], [_CODES[c] for c in args]
+    except (KeyError, ValueError):
+        raise HipKernelError("%s: signature %r has a type code this module does not know" % (name, sig)) from None
+
+
+def _bind(lib, prefix):
+    """Set argtypes / restype of every function in `lib`'s signature table; name -> signature."""
+    try:
+        boot = {n: getattr(lib, prefix + n) for n in _BOOT}
+    except AttributeError:
+        raise HipKernelError("%s has no signature table (%s_count): it was built before the table existed, "
+                             "so no call into it can be typed" % (lib._name, prefix)) from None
+    for n, f in boot.items():
+        f.restype, f.argtypes = decode(prefix + n, _BOOT[n])
+    sigs = dict(boot["_entry"](i).decode().split(" ") for i in range(boot["_count"]()))
+    for name, sig in sigs.items():
+        f = getattr(lib, name)
+        f.restype, f.argtypes = decode(name, sig)
+    return sigs
+
+
+def _check_size(cls, size):
+    if ctypes.sizeof(cls) != size:
+        raise HipKernelError("ops._lib.%s (%d bytes) does not match its C struct (%d bytes)"
+                             % (cls.__name__, ctypes.sizeof(cls), size))
+
+
+_sigs = {}
+
+
+def hip():
+    """libttd_hip.so with every export typed; checks the three struct mirrors field by field."""
+    lib = _native.hip()
+    if "hip" not in _sigs:
+        sigs = _bind(lib, "ttdk_abi")
+        for code, cls in _STRUCTS.items():
+            out = (c_longlong * 64)()
+            n = lib.ttdk_abi_layout(ord(code), out, len(out))
+            mine = [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f, _ in cls._fields_]
+            if mine != list(out[:max(n, 0)]):
+                raise HipKernelError("ops._lib.%s does not match its C struct: size and field offsets %s here, %s in %s"
+                                     % (cls.__name__, mine, list(out[:max(n, 0)]), lib._name))
+        _sigs["hip"] = sigs
+    return lib
+
+
+def rt():
+    """libttd_rt.so with its plan exports typed (the other ttd_* exports keep their own bindings)."""
+    lib = _native.rt()
+    if "rt" not in _sigs:
+        sigs = _bind(lib, "ttd_abi")
+        _check_size(ConvGeom, lib.ttd_plan_conv_size())
+        _check_size(DwConvGeom, lib.ttd_dwplan_geom_size())
+        _sigs["rt"] = sigs
+    return lib
+
+
+def signatures(kind):
+    """name -> ``ret:args`` of every typed export of the "hip" or "rt" library."""
+    (hip if kind == "hip" else rt)()
+    return _sigs[kind]
+
+
+def _typed(kind, name):
+    sig = signatures(kind).get(name)
+    if sig is None:
+        raise HipKernelError("%s is not in the signature table of libttd_%s.so" % (name, kind))
+    return getattr((_native.hip if kind == "hip" else _native.rt)(), name), sig
+
+
+def rt_fn(name):
+    """Plan export `name` of libttd_rt.so."""
+    return _typed("rt", name)[0]
+
+
+_fns = {}  # name -> (function, number of arguments, return code)
+
+
+def _entry(name):
+    e = _fns.get(name)
+    if e is None:
+        f, sig = _typed("hip", name)
+        e = _fns[name] = (f, len(sig) - 2, sig[0])
+    return e
 
 
 def fn(name):
-    f = _fns.get(name)
-    if f is None:
-        lib = _native.hip()
-        f = getattr(lib, name)
-        f.argtypes = _SIGS[name]
-        f.restype = _RESTYPE.get(name, c_int)
-        _fns[name] = f
-    return f
+    return _entry(name)[0]
 
 
-class HipKernelError(RuntimeError):
-    pass
+def _arity(name, n, given):
+    # ctypes itself only catches too few arguments: a surplus one would be passed along
+    raise TypeError("%s takes %d arguments, %d given" % (name, n, given))
 
 
 # Per-launch timing for profiling tools (TTD_OP_TIMING=1): every call is bracketed by HIP
@@ -189,22 +174,30 @@ def label(x):
 
 
 def call(name, *args):
+    f, n, ret = _fns.get(name) or _entry(name)
+    if len(args) != n:
+        _arity(name, n, len(args))
+    if ret != "i":
+        raise TypeError("%s returns %r, not a hipError_t: use query()" % (name, ret))
     if TIMING is not None:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
-        rc = fn(name)(*args)
+        rc = f(*args)
         e.record()
         TIMING.append((name, list(_labels), s, e))
         _labels.clear()
     else:
-        rc = fn(name)(*args)
+        rc = f(*args)
     if rc != 0:
         raise HipKernelError("%s failed with hipError_t %d" % (name, rc))
 
 
 def query(name, *args):
     """Call a host-side helper that returns a plain int (not a hipError_t)."""
-    return fn(name)(*args)
+    f, n, _ = _fns.get(name) or _entry(name)
+    if len(args) != n:
+        _arity(name, n, len(args))
+    return f(*args)
 
 
 def stream():

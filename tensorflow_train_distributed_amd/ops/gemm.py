@@ -141,11 +141,6 @@ def gemm(a, b, *, trans_a=False, trans_b=False, out=None, out_dtype=torch.bfloat
     return out
 
 
-_lib.register({"ttdk_gemm4w_bf16": [_lib.P, _lib.L, _lib.P, _lib.L, _lib.I, _lib.I, _lib.I, _lib.E, _lib.P],
-               "ttdk_set_g4_sched": [_lib.I], "ttdk_set_g4_group": [_lib.I],
-               "ttdk_set_g4_stagger": [_lib.I]})
-
-
 def set_g4_stagger(v: int) -> int:
     """Stagger the persistent 4-wave GEMM's workgroup tile phases (1) or not (0); returns the
     previous setting."""
@@ -182,12 +177,6 @@ def gemm4w(a, b, *, out=None, bias=None, act=ACT_NONE, residual=None, beta=0, al
     _lib.call("ttdk_gemm4w_bf16", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), M, N, K, ctypes.byref(e),
               _lib.stream())
     return out
-
-
-_lib.register({"ttdk_gemm_bf16_batched": [_lib.P, _lib.L, _lib.L, _lib.I, _lib.P, _lib.L, _lib.L, _lib.I, _lib.P,
-                                          _lib.L, _lib.L, _lib.I, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P],
-               "ttdk_gemm_f32_batched": [_lib.P, _lib.L, _lib.L, _lib.I, _lib.P, _lib.L, _lib.L, _lib.I, _lib.P,
-                                         _lib.L, _lib.L, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P]})
 
 
 def gemm_batched(a, b, *, trans_a=False, trans_b=False, out_dtype=torch.float32):
@@ -289,25 +278,16 @@ def gemm4t(dy, x, out=None, bias_out=None, *, splits=1, beta=0, alpha=1.0):
 _C3 = _os.environ.get("TTD_CONV3", "1") != "0"
 
 
-_lib.register({"ttdk_set_conv3_s3": [_lib.I]})
-
-
 def set_conv3_s3(on: bool) -> bool:
     """Switch the stage-3 (28 x 28, 128 -> 128) streamed-filter halo conv on / off (TTD_CONV3_S3);
     returns the previous setting. Takes effect for convs dispatched afterwards."""
     return bool(_lib.query("ttdk_set_conv3_s3", 1 if on else 0))
 
 
-_lib.register({"ttdk_set_conv3_sched": [_lib.I]})
-
-
 def set_conv3_sched(new: bool) -> bool:
     """Switch both halo 3x3 kernels between their current schedule and its predecessor
     (TTD_CONV3_SCHED; an A/B switch: results are bit-identical); returns the previous setting."""
     return bool(_lib.query("ttdk_set_conv3_sched", 1 if new else 0))
-
-
-_lib.register({"ttdk_set_conv3_feed": [_lib.I]})
 
 
 def set_conv3_feed(new: bool) -> bool:
@@ -1092,13 +1072,6 @@ def stem_wgrad(x, g_out, y, coef, *, out=None, beta=0):
 
 
 # ------------------------------------------------------------------ fp8 (gfx950 block-scaled MFMA)
-_lib.register({
-    "ttdk_conv_fwd_fp8": [_lib.P, _lib.P, _lib.G, _lib.I, _lib.E, _lib.P],
-    "ttdk_gemm_fp8": [_lib.P, _lib.L, _lib.P, _lib.L, _lib.I, _lib.I, _lib.I, _lib.I, _lib.I, _lib.E, _lib.P],
-    "ttdk_conv_dgrad_fp8": [_lib.P, _lib.P, _lib.G, _lib.E, _lib.P],
-})
-
-
 def gemm_fp8(a8, b8, *, alpha=1.0, out=None, out_dtype=torch.bfloat16, bias=None, act=ACT_NONE, residual=None,
              beta=0, splits=1, a_e5m2=False, aux=None):
     """C[M, N] = alpha * A[M, K] . B[N, K]^T with fp8 operands (uint8 storage: OCP e4m3, or

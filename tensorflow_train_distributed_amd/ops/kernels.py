@@ -489,31 +489,6 @@ def sumsq(x, out=None):
 
 
 # ------------------------------------------------------------------ shape-general ttd.nn kernels (nn_generic.hip)
-_lib.register({
-    "ttdk_col_stats_parts": [_lib.L, _lib.I],
-    "ttdk_col_stats": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.I, _lib.L, _lib.I, _lib.P, _lib.I, _lib.P],
-    "ttdk_col_reduce2": [_lib.P, _lib.I, _lib.I, _lib.P, _lib.P, _lib.I, _lib.P],
-    "ttdk_col_affine": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.I, _lib.P],
-    "ttdk_bn_infer_coef": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.F, _lib.I, _lib.P, _lib.P, _lib.P, _lib.P],
-    "ttdk_bn_infer_bwd": [_lib.P, _lib.I, _lib.I, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P],
-    "ttdk_maxpool_generic_fwd": [_lib.P, _lib.P, _lib.P, _lib.I] + [_lib.I] * 12 + [_lib.P],
-    "ttdk_maxpool_generic_bwd": [_lib.P, _lib.P, _lib.P, _lib.I] + [_lib.I] * 12 + [_lib.P],
-    "ttdk_gap_fwd": [_lib.P, _lib.P, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P],
-    "ttdk_gap_bwd": [_lib.P, _lib.P, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P],
-    "ttdk_ln_generic_fwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.F, _lib.P],
-    "ttdk_ln_generic_bwd_dx": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.P],
-    "ttdk_rms_generic_fwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.F, _lib.P],
-    "ttdk_rms_generic_parts": [_lib.L, _lib.I],
-    "ttdk_rms_generic_bwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.I, _lib.L, _lib.I,
-                             _lib.P],
-    "ttdk_gather_generic": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.I, _lib.L, _lib.I, _lib.L, _lib.P],
-    "ttdk_scatter_add_generic": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.I, _lib.L, _lib.I, _lib.L, _lib.P],
-    "ttdk_in_top_k": [_lib.P, _lib.P, _lib.I, _lib.P, _lib.I, _lib.L, _lib.I, _lib.I, _lib.P],
-    "ttdk_unary": [_lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.P],
-    "ttdk_unary_bwd": [_lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.P],
-})
-
-
 def _dt(*ts):
     d = ts[0].dtype
     for t in ts:
@@ -640,14 +615,6 @@ def rms_generic_bwd(dy2d, x2d, gamma, rstd, dgamma, want_dx=True, accumulate=Fal
 
 
 # ------------------------------------------------------------------ depthwise convolution (depthwise.hip)
-_lib.register({
-    "ttdk_dwconv_fwd": [_lib.P, _lib.P, _lib.P, _lib.I, _lib.DG, _lib.I, _lib.P],
-    "ttdk_dwconv_dgrad": [_lib.P, _lib.P, _lib.P, _lib.I, _lib.DG, _lib.I, _lib.P],
-    "ttdk_dwconv_wgrad": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.I, _lib.DG, _lib.I, _lib.I, _lib.P],
-    "ttdk_dwconv_wgrad_parts": [_lib.DG],
-    "ttdk_dwconv_wgrad_ws_floats": [_lib.DG],
-})
-
 # strides, top / left padding, dilations and the output extent; the bottom / right padding follows
 # from P and Q (TF's SAME: ph = total // 2 with P = ceil(H / sh))
 DwGeom = namedtuple("DwGeom", "sh sw ph pw dh dw P Q")
@@ -742,15 +709,6 @@ def dwconv_wgrad(x, dy, w_shape, geom, out=None, accumulate=False, workspace=Non
 
 
 # ------------------------------------------------------------------ group normalisation (groupnorm.hip)
-_lib.register({
-    "ttdk_group_norm_fwd": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.L, _lib.L, _lib.I,
-                            _lib.I, _lib.F, _lib.I, _lib.I, _lib.P],
-    "ttdk_group_norm_bwd_stats": [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.L, _lib.L,
-                                  _lib.L, _lib.I, _lib.I, _lib.I, _lib.I, _lib.I, _lib.P],
-    "ttdk_group_norm_bwd_dx": [_lib.P, _lib.P, _lib.P, _lib.L, _lib.P, _lib.L, _lib.L, _lib.I, _lib.I, _lib.I, _lib.I,
-                               _lib.P],
-})
-
 _GN_FORMS = {"auto": 0, "generic": 1}
 
 
@@ -907,14 +865,6 @@ def unary_bwd(dy, y, op):
     return dx
 
 
-_lib.register({
-    "ttdk_sum_blocks": [_lib.L],
-    "ttdk_sum_all": [_lib.P, _lib.I, _lib.L, _lib.P, _lib.F, _lib.P, _lib.P],
-    "ttdk_fill_scaled": [_lib.P, _lib.I, _lib.L, _lib.P, _lib.F, _lib.P],
-    "ttdk_row_scale": [_lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.P],
-})
-
-
 def sum_all(x, scale=1.0):
     """0-d tensor = scale * sum(x) (deterministic two-stage reduction), same dtype as x."""
     n = x.numel()
@@ -937,10 +887,6 @@ def row_scale(a2d, g):
     out = torch.empty_like(a2d)
     _lib.call("ttdk_row_scale", a2d.data_ptr(), g.data_ptr(), out.data_ptr(), _dt(a2d, out), rows, C, _s())
     return out
-
-
-_lib.register({"ttdk_zero": [_lib.P, _lib.L, _lib.P], "ttdk_trace_marker": [_lib.I, _lib.P],
-               "ttdk_copy": [_lib.P, _lib.P, _lib.L, _lib.P]})
 
 
 def concat_(out, parts):
@@ -978,8 +924,6 @@ def trace_marker(tag=0):
 
 
 # ------------------------------------------------------------------ device initialisation (init.hip)
-_lib.register({"ttdk_init_random": [_lib.P, _lib.L, _lib.I, _lib.F, _lib.F, _lib.U64, _lib.U64, _lib.P]})
-
 INIT_NORMAL, INIT_TRUNCATED, INIT_UNIFORM, INIT_CONSTANT = 0, 1, 2, 3
 
 

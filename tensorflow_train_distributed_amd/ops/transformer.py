@@ -11,38 +11,6 @@ import torch
 
 from ..utils.errors import InvalidArgumentError
 from . import _lib
-from ._lib import F, I, L, P
-
-_lib.register({
-    "ttdk_attn_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, I, P],
-    "ttdk_attn_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, I, P],
-    "ttdk_attn_set_fused_bwd": [I],
-    "ttdk_attn_band": [P, P, I, I, I, I, I, P, P],
-    "ttdk_attn_band_fwd": [P, L, P, L, P, L, P, L, P, P, I, I, I, I, I, F, P, I, P],
-    "ttdk_attn_band_bwd": [P, L, P, L, P, L, P, L, P, L, P, P, P, L, P, L, P, L, P, I, I, I, I, I, F, P, I, P],
-    "ttdk_ln_fwd": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
-    "ttdk_ln_bwd_num_blocks": [I],
-    "ttdk_ln_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, F, I, F, I, P, P],
-    "ttdk_colreduce": [P, I, I, I, P, I, P],
-    "ttdk_embed_fwd": [P, P, P, P, P, P, L, I, I, P],
-    "ttdk_embed_bwd": [P, P, P, P, P, P, I, I, I, I, I, P],
-    "ttdk_gather_rows": [P, L, P, I, L, P, I, I, P],
-    "ttdk_scatter_rows": [P, P, I, L, P, L, I, I, I, P],
-    "ttdk_rng_advance": [P, P],
-    "ttdk_count_valid": [P, I, F, P, P],
-    "ttdk_count_valid2": [P, I, F, P, P],
-    "ttdk_xent_vocab": [P, L, I, P, I, P, P, P, P, P],
-    "ttdk_tanh_bf16": [P, L, P],
-    "ttdk_dact_bf16": [P, P, P, L, I, P],
-    "ttdk_rope": [P, L, P, L, I, P, I, L, I, I, I, I, P],
-    "ttdk_rope_max_threads": [],
-    "ttdk_rms_fwd": [P, P, P, P, P, P, I, I, F, F, I, F, I, P, P],
-    "ttdk_rms_bwd_num_blocks": [I],
-    "ttdk_rms_bwd": [P, P, P, P, P, P, P, P, I, I, I, F, I, F, I, P, P],
-    "ttdk_swiglu_fwd": [P, L, P, L, I, L, I, P],
-    "ttdk_swiglu_bwd": [P, L, P, L, P, L, I, L, I, P],
-    "ttdk_swiglu_max_threads": [],
-})
 
 
 def _p(t):

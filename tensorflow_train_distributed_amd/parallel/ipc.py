@@ -31,61 +31,19 @@ from __future__ import annotations
 import ctypes
 import os
 import socket
-from ctypes import c_char_p, c_int, c_longlong, c_void_p
+from ctypes import c_int, c_longlong
 from typing import List, Optional
 
 import torch
 import torch.distributed as dist
 
-from .. import _native
+from ..ops._lib import hip as _hip, rt as _rt  # ttdi_* / ttd_ipc_*: typed from the libraries' signature tables
 from ..utils import errors
 
 RCCL, ONE_SHOT, TWO_SHOT = 0, 1, 2
 ONE_SHOT_MAX = 1 << 20  # ipc_plan.h kOneShotMax
 PATH_NAMES = {RCCL: "rccl", ONE_SHOT: "ipc_oneshot", TWO_SHOT: "ipc_twoshot"}
 HANDLE_BYTES = 128  # data + flags hipIpcMemHandle_t
-
-_bound = False
-
-
-def _hip():
-    global _bound
-    lib = _native.hip()
-    if not _bound:
-        lib.ttdi_create.restype = c_void_p
-        lib.ttdi_create.argtypes = [c_int, c_int, c_int, c_longlong, c_longlong]
-        lib.ttdi_handle.restype = c_int
-        lib.ttdi_handle.argtypes = [c_void_p, c_char_p]
-        lib.ttdi_open.restype = c_int
-        lib.ttdi_open.argtypes = [c_void_p, c_char_p, ctypes.POINTER(c_int)]
-        lib.ttdi_allreduce.restype = c_int
-        lib.ttdi_allreduce.argtypes = [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p]
-        lib.ttdi_link_local.restype = c_int
-        lib.ttdi_link_local.argtypes = [c_void_p, c_void_p]
-        lib.ttdi_error.restype = c_int
-        lib.ttdi_error.argtypes = [c_void_p]
-        lib.ttdi_clear_error.restype = None
-        lib.ttdi_clear_error.argtypes = [c_void_p]
-        lib.ttdi_destroy.restype = None
-        lib.ttdi_destroy.argtypes = [c_void_p]
-        _bound = True
-    return lib
-
-
-def _rt():
-    lib = _native.rt()
-    lib.ttd_ipc_choose.restype = c_int
-    lib.ttd_ipc_choose.argtypes = [c_longlong, c_int, c_int, c_longlong]
-    lib.ttd_ipc_chunk.restype = None
-    lib.ttd_ipc_chunk.argtypes = [c_longlong, c_int, c_int, c_int, ctypes.POINTER(c_longlong),
-                                  ctypes.POINTER(c_longlong)]
-    lib.ttd_ipc_part.restype = None
-    lib.ttd_ipc_part.argtypes = [c_longlong, c_longlong, c_int, c_int, c_int, ctypes.POINTER(c_longlong),
-                                 ctypes.POINTER(c_longlong)]
-    lib.ttd_ipc_blocks.restype = c_int
-    lib.ttd_ipc_blocks.argtypes = [c_longlong, c_int]
-    return lib
-
 
 def default_cap() -> int:
     return int(float(os.environ.get("TTD_IPC_AR_CAP_MB", "8")) * (1 << 20))

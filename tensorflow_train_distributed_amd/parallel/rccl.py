@@ -44,69 +44,18 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_void_p
+from ctypes import c_float
 from typing import Dict, List, Optional
 
 import torch
 import torch.distributed as dist
 
-from .. import _native
+from ..ops._lib import hip as _lib  # ttdc_* and the reserved-CU switches: typed from the library's signature table
 from ..utils import errors
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float64: 2, torch.int32: 3, torch.int64: 4, torch.uint8: 5}
 _OP = {"sum": 0, "avg": 1, "min": 2, "max": 3}
 _ALGO = {"allreduce": 0, "hierarchical": 1, "reduce_to_one": 2}
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = _native.hip()
-    if not _bound:
-        lib.ttdc_error.restype = c_char_p
-        lib.ttdc_error.argtypes = [c_void_p]
-        lib.ttdc_version.restype = c_int
-        lib.ttdc_unique_id.restype = c_int
-        lib.ttdc_unique_id.argtypes = [c_char_p]
-        lib.ttdc_create.restype = c_void_p
-        lib.ttdc_create.argtypes = [c_char_p, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int]
-        lib.ttdc_stream.restype = c_void_p
-        lib.ttdc_stream.argtypes = [c_void_p]
-        lib.ttdc_bucket.restype = c_int
-        lib.ttdc_bucket.argtypes = [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p]
-        lib.ttdc_bucket_nofork.restype = c_int
-        lib.ttdc_bucket_nofork.argtypes = [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int]
-        lib.ttdc_join.restype = c_int
-        lib.ttdc_join.argtypes = [c_void_p, c_void_p]
-        lib.ttdc_arm.restype = c_int
-        lib.ttdc_arm.argtypes = [c_void_p, c_void_p]
-        lib.ttdc_collective.restype = c_int
-        lib.ttdc_collective.argtypes = [c_void_p, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p]
-        lib.ttdc_synchronize.restype = c_int
-        lib.ttdc_synchronize.argtypes = [c_void_p]
-        lib.ttdc_probe.restype = c_int
-        lib.ttdc_probe.argtypes = [c_void_p, c_void_p, c_longlong, c_int, ctypes.POINTER(c_float)]
-        lib.ttdc_set_timing.restype = None
-        lib.ttdc_set_timing.argtypes = [c_void_p, c_int]
-        lib.ttdc_timing.restype = c_int
-        lib.ttdc_timing.argtypes = [c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_float)]
-        lib.ttdc_destroy.restype = None
-        lib.ttdc_destroy.argtypes = [c_void_p, c_int]
-        lib.ttdc_reserve.restype = c_int
-        lib.ttdc_reserve.argtypes = [c_void_p, c_longlong]
-        lib.ttdc_aborts.restype = c_int
-        lib.ttdc_aborts.argtypes = [c_void_p]
-        lib.ttdc_debug_stall.restype = c_int
-        lib.ttdc_debug_stall.argtypes = [c_void_p, c_void_p, c_int]
-        lib.ttdc_emulate_bucket.restype = c_int
-        lib.ttdc_emulate_bucket.argtypes = [c_void_p, c_int, c_double, c_void_p, c_longlong]
-        lib.ttdk_set_reserved_cus.restype = c_int
-        lib.ttdk_set_reserved_cus.argtypes = [c_int]
-        lib.ttdk_persistent_cus.restype = c_int
-        lib.ttdk_persistent_cus.argtypes = []
-        _bound = True
-    return lib
 
 
 def rccl_version() -> int:
