@@ -469,6 +469,7 @@ TTDK_API(int, ttdk_maxpool_generic_fwd, (const void* x, void* y, uint8_t* arg, i
 TTDK_API(int, ttdk_maxpool_generic_bwd, (const void* dy, const uint8_t* arg, void* dx, int dt, int N, int H, int W,
                                          int C, int P, int Q, int R, int S, int sh, int sw, int ph, int pw,
                                          hipStream_t st)) {
+  if (R * S > 255 || ph >= R || pw >= S || P <= 0 || Q <= 0) return hipErrorInvalidValue;  // as the forward
   const long long total = static_cast<long long>(N) * H * W * C;
   if (dt == 0)
     hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)dy, arg,

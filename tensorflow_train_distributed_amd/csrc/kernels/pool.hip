@@ -26,6 +26,7 @@ __global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
       best[j] = -INFINITY;
       bi[j] = 0;
     }
+    bool any = false;  // the first tap inside the input is taken as it is: arg never names padding
     for (int r = 0; r < R; ++r) {
       const int h = p * sh - ph + r;
       if (h < 0 || h >= H) continue;
@@ -36,10 +37,11 @@ __global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
         unpack8(*reinterpret_cast<const uint4*>(x + ((static_cast<long long>(n) * H + h) * W + w) * C + c8 * 8), f);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          if (f[j] > best[j] || (f[j] != f[j])) {  // NaN propagates
+          if (!any || f[j] > best[j] || (f[j] != f[j])) {  // NaN propagates
             best[j] = f[j];
             bi[j] = r * S + s;
           }
+        any = true;
       }
     }
     reinterpret_cast<uint4*>(y)[i] = pack8(best);
@@ -188,6 +190,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const bf16_t* __re
       bi[j] = 0;
     }
     uint32_t mbits[2][2] = {{0, 0}, {0, 0}};
+    bool any = false;  // as in maxpool_fwd_kernel
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -205,11 +208,12 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const bf16_t* __re
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           mb |= (o[j] > 0.f ? 1u : 0u) << j;
-          if (o[j] > best[j] || (o[j] != o[j])) {
+          if (!any || o[j] > best[j] || (o[j] != o[j])) {
             best[j] = o[j];
             bi[j] = r * 3 + s;
           }
         }
+        any = true;
         if (r >= 1 && s >= 1) mbits[r - 1][s - 1] = mb;
       }
     reinterpret_cast<uint4*>(out)[i] = pack8(best);
@@ -329,6 +333,12 @@ inline int grid_for(long long n) {
   return static_cast<int>(g < 16384 ? (g < 1 ? 1 : g) : 16384);
 }
 
+// What ttdk_maxpool_generic_fwd accepts: the argmax fits a byte, the padding is smaller than the
+// window (no window of a P x Q that follows from it lies wholly in padding) and there is an output.
+inline bool pool_geometry_ok(int P, int Q, int R, int S, int ph, int pw) {
+  return R > 0 && S > 0 && R * S <= 255 && ph >= 0 && pw >= 0 && ph < R && pw < S && P > 0 && Q > 0;
+}
+
 }  // namespace
 }  // namespace ttdk
 
@@ -336,7 +346,7 @@ using namespace ttdk;
 
 TTDK_API(int, ttdk_maxpool_fwd, (const bf16_t* x, bf16_t* y, uint8_t* arg, int N, int H, int W, int C, int P, int Q,
                                  int R, int S, int sh, int sw, int ph, int pw, hipStream_t st)) {
-  if (C % 8 || R * S > 255) return hipErrorInvalidValue;
+  if (C % 8 || !pool_geometry_ok(P, Q, R, S, ph, pw)) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(N) * P * Q * (C / 8);
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, x, y, arg, N, H, W, C, P, Q, R, S,
                      sh, sw, ph, pw);
@@ -345,7 +355,7 @@ TTDK_API(int, ttdk_maxpool_fwd, (const bf16_t* x, bf16_t* y, uint8_t* arg, int N
 
 TTDK_API(int, ttdk_maxpool_bwd, (const bf16_t* dy, const uint8_t* arg, bf16_t* dx, int N, int H, int W, int C, int P,
                                  int Q, int R, int S, int sh, int sw, int ph, int pw, hipStream_t st)) {
-  if (C % 8) return hipErrorInvalidValue;
+  if (C % 8 || !pool_geometry_ok(P, Q, R, S, ph, pw)) return hipErrorInvalidValue;
   const long long total = static_cast<long long>(N) * H * W * (C / 8);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, dy, arg, dx, N, H, W, C, P, Q, R, S,
                      sh, sw, ph, pw);

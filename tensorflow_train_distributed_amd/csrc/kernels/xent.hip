@@ -70,12 +70,14 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* __restrict__ logits,
     if (correct) correct[row] = ok;
     if (part) {  // per-row terms; xent_sums_kernel reduces them in a fixed order (deterministic)
       part[2 * row] = loss * inv_rows;
-      part[2 * row + 1] = (ok ? 1.f : 0.f) * inv_rows;
+      part[2 * row + 1] = ok ? 1.f : 0.f;  // a count: summed exactly, divided once
     }
   }
 }
 
-// sums[0..1] = sum over rows of part[row][0..1], one block, fixed order.
+// sums[0] = sum over rows of part[row][0] (loss / rows), sums[1] = (sum of part[row][1]) / rows (the
+// count of correct rows, exact in fp32, so the mean accuracy carries one rounding and k of k rows
+// correct is 1 and never above it); one block, fixed order.
 __global__ __launch_bounds__(256) void xent_sums_kernel(const float* __restrict__ part, int rows,
                                                         float* __restrict__ sums) {
   __shared__ float red[16];
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(256) void xent_sums_kernel(const float* __restrict_
   b = block_sum(b, red + 8);
   if (threadIdx.x == 0) {
     sums[0] = a;
-    sums[1] = b;
+    sums[1] = b / static_cast<float>(rows);
   }
 }
 
@@ -104,6 +106,8 @@ TTDK_API(int, ttdk_sparse_xent, (const void* logits, int logits_dtype, const voi
                                  int V, float grad_scale, float* loss_rows, void* dlogits, uint8_t* correct,
                                  float* sums, float* part, hipStream_t st)) {
   if (sums && !part) return hipErrorInvalidValue;
+  if (logits_dtype < 0 || logits_dtype > 1 || label_dtype < 0 || label_dtype > 1 || rows <= 0 || V <= 0)
+    return hipErrorInvalidValue;
   const float inv = 1.f / rows;
   dim3 g(rows), b(256);
 #define TTDK_X(T, L)                                                                                              \
