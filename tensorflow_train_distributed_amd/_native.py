@@ -109,7 +109,14 @@ def hip_sources():
 # Per-file extra flags. attention.hip: no SLP vectorisation — -O3 packs adjacent f32 multiplies /
 # FMAs of the softmax into v_pk_*_f32, which beside MFMAs cost more issue cycles than the scalar
 # pair (cdna_hip_programming.md, attention prefill pitfalls).
-_FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"]}
+# attention128.hip: the same reason applies — its softmax is the same adjacent f32 FMAs beside MFMAs
+# (a cost argument carried over from the 64-wide file, not measured again at 128) — and, like
+# rope.hip since its head-size template, it is built without the packed fp32 instructions
+# altogether (the float4 multiplies of the O rescale would otherwise still become v_pk_mul_f32).
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+_FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"],
+               "attention128.hip": ["-fno-slp-vectorize", *_NO_PK_F32],
+               "rope.hip": _NO_PK_F32}
 
 
 def build_hip(force: bool = False) -> str:

@@ -85,6 +85,7 @@
 namespace ttdk {
 namespace {
 
+using tile::causal_block;
 using tile::mfma;
 using tile::off64;
 using tile::pack_frag;
@@ -223,28 +224,6 @@ struct TileLoader {
 };
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// Causal workgroups do unequal work (block b of a head streams 2b + 2 tiles in fwd / bwd_q, and
-// 2 (nblk - b) in bwd_kv), and the nblk blocks of a head stay adjacent in the grid (they share
-// K / V or Q / dO in one XCD's L2). Which block the j-th work item of head bh takes:
-//   order 0  natural (j);
-//   order 1  heavy first: the longest block of each head first. Measured no better than natural,
-//            and both about as slow as if every block were the longest: the grid then has period
-//            nblk, workgroups reach the CUs round-robin, so a CU keeps drawing the same block
-//            index and the CUs that draw the long one set the kernel's time;
-//   order 2  rotated: j plus the base-4 digit sum of bh. Over every power-of-two stride of the
-//            grid the block index then cycles evenly, so every CU gets the same mix.
-// (profiles/attn_causal_bench.txt)
-__device__ __forceinline__ int causal_block(int j, int bh, int nblk, int order, bool long_last) {
-  if (order == 2) {
-    uint32_t x = static_cast<uint32_t>(bh);
-    x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
-    x = (x + (x >> 4)) & 0x0f0f0f0fu;
-    x = (x * 0x01010101u) >> 24;  // sum of the base-4 digits (<= 48)
-    return static_cast<int>((static_cast<uint32_t>(j) + x) % static_cast<uint32_t>(nblk));
-  }
-  return order == 1 && long_last ? nblk - 1 - j : j;
-}
 
 // ------------------------------------------------------------------------------ forward
 // (launch_bounds(256, 4) — 128 VGPRs, 4 waves / SIMD instead of 3, 10-12 spilled — measured

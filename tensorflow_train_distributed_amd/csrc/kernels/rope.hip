@@ -1,5 +1,6 @@
 // Rotary position embeddings (RoPE), half-split convention ("rotate_half", LLaMA / GPT-NeoX), head
-// size 64. For a token at position p and i in [0, 32), theta_i = base^(-i/32):
+// size 64 or 128 (HALF = 32 or 64, a template parameter: below, 64 and 32 stand for 2 HALF and HALF
+// of the 64-wide form). For a token at position p and i in [0, 32), theta_i = base^(-i/32):
 //   y[i]      = x[i]      * cos(p theta_i) - x[i + 32] * sin(p theta_i)
 //   y[i + 32] = x[i + 32] * cos(p theta_i) + x[i]      * sin(p theta_i)
 // inverse uses -sin: the transpose of the rotation, so both its inverse and its backward.
@@ -71,31 +72,31 @@ __device__ __forceinline__ void load_table(const float* __restrict__ p, float (&
 // Step of the grid-stride loop, in (row, in-row item, position) form: one stride of
 // gridDim.x * 256 work items is drow rows and drem items further, dpos = drow % S.
 struct RopeStep {
-  int per_row;  // heads * (32 / E) work items per row
+  int per_row;  // heads * (HALF / E) work items per row
   int drow, drem, dpos;
 };
 
 // x and y may be the same buffer: no __restrict__ on them.
-template <typename T>
+template <typename T, int HALF>
 __global__ __launch_bounds__(kRopeBlock) void rope_kernel(const T* x, long long ldx, T* y, long long ldy,
                                                           const float* __restrict__ table, long long tokens, int S,
                                                           int pos0, float sgn, RopeStep st) {
   constexpr int E = RopeVec<T>::E;
-  constexpr int CH = 32 / E;  // chunks per half head
+  constexpr int CH = HALF / E;  // chunks per half head
   const unsigned i0 = blockIdx.x * kRopeBlock + threadIdx.x;  // < 2048 * 256
   long long r = i0 / static_cast<unsigned>(st.per_row);
   int j = static_cast<int>(i0 % static_cast<unsigned>(st.per_row));
   int p = static_cast<int>(r % S);
   while (r < tokens) {
     const int h = j / CH, c = j % CH;
-    const long long col = static_cast<long long>(h) * 64 + c * E;
+    const long long col = static_cast<long long>(h) * (2 * HALF) + c * E;
     const T* xp = x + r * ldx + col;
-    const float* tp = table + static_cast<long long>(pos0 + p) * 64 + c * E;
+    const float* tp = table + static_cast<long long>(pos0 + p) * (2 * HALF) + c * E;
     float lo[E], hi[E], cs[E], sn[E], ylo[E], yhi[E];
     RopeVec<T>::load(xp, lo);
-    RopeVec<T>::load(xp + 32, hi);
+    RopeVec<T>::load(xp + HALF, hi);
     load_table<E>(tp, cs);
-    load_table<E>(tp + 32, sn);
+    load_table<E>(tp + HALF, sn);
 #pragma unroll
     for (int k = 0; k < E; ++k) {
       const float s = sn[k] * sgn;
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kRopeBlock) void rope_kernel(const T* x, long long 
     }
     T* yp = y + r * ldy + col;
     RopeVec<T>::store(yp, ylo);
-    RopeVec<T>::store(yp + 32, yhi);
+    RopeVec<T>::store(yp + HALF, yhi);
     // advance one grid stride
     j += st.drem;
     r += st.drow;
@@ -118,12 +119,12 @@ __global__ __launch_bounds__(kRopeBlock) void rope_kernel(const T* x, long long 
   }
 }
 
-template <typename T>
+template <typename T, int HALF>
 int rope_launch(const void* x, long long ldx, void* y, long long ldy, const float* table, long long tokens, int S,
                 int heads, int pos0, int inverse, hipStream_t st) {
   constexpr int E = RopeVec<T>::E;
   RopeStep step;
-  step.per_row = heads * (32 / E);
+  step.per_row = heads * (HALF / E);
   const long long items = tokens * step.per_row;
   long long blocks = (items + kRopeBlock - 1) / kRopeBlock;
   if (blocks > kRopeMaxBlocks) blocks = kRopeMaxBlocks;
@@ -131,7 +132,7 @@ int rope_launch(const void* x, long long ldx, void* y, long long ldy, const floa
   step.drow = stride / step.per_row;
   step.drem = stride % step.per_row;
   step.dpos = step.drow % S;
-  hipLaunchKernelGGL(rope_kernel<T>, dim3(static_cast<unsigned>(blocks)), dim3(kRopeBlock), 0, st,
+  hipLaunchKernelGGL((rope_kernel<T, HALF>), dim3(static_cast<unsigned>(blocks)), dim3(kRopeBlock), 0, st,
                      static_cast<const T*>(x), ldx, static_cast<T*>(y), ldy, table, tokens, S, pos0,
                      inverse ? -1.f : 1.f, step);
   return hipGetLastError();
@@ -147,6 +148,26 @@ using namespace ttdk;
 // Number of threads the capped grid launches (tests size their grid-stride case from it).
 TTDK_API(int, ttdk_rope_max_threads, ()) { return kRopeMaxBlocks * kRopeBlock; }
 
+namespace {
+// The checks and the launch of both exports; HALF = head_dim / 2.
+template <int HALF>
+int rope_call(const void* x, long long ldx, void* y, long long ldy, int dt, const float* table, int table_rows,
+              long long tokens, int S, int heads, int pos0, int inverse, hipStream_t st) {
+  if (heads <= 0 || heads > (1 << 20) || S <= 0 || tokens < 0) return hipErrorInvalidValue;
+  if (tokens % S != 0) return hipErrorInvalidValue;
+  if (pos0 < 0 || static_cast<long long>(pos0) + S > table_rows) return hipErrorInvalidValue;
+  if (dt != 0 && dt != 1) return hipErrorInvalidValue;
+  const long long width = static_cast<long long>(heads) * (2 * HALF);
+  if (ldx < width || ldy < width) return hipErrorInvalidValue;
+  const long long esz = dt == 0 ? 4 : 2;
+  if (!x || !y || !table || !aligned16(x) || !aligned16(y) || !aligned16(table)) return hipErrorInvalidValue;
+  if ((ldx * esz) % 16 != 0 || (ldy * esz) % 16 != 0) return hipErrorInvalidValue;
+  if (tokens == 0) return 0;
+  if (dt == 0) return rope_launch<float, HALF>(x, ldx, y, ldy, table, tokens, S, heads, pos0, inverse, st);
+  return rope_launch<bf16_t, HALF>(x, ldx, y, ldy, table, tokens, S, heads, pos0, inverse, st);
+}
+}  // namespace
+
 // y[r, :heads*64] = rotation of x[r, :heads*64] at position pos0 + r % S (inverse != 0: the inverse
 // rotation). x, y: [tokens, >= heads*64], row strides ldx / ldy in elements, type dt (0 fp32, 1 bf16);
 // table fp32 [table_rows][2][32]. y == x with ldy == ldx is in place; any other overlap is the
@@ -154,16 +175,15 @@ TTDK_API(int, ttdk_rope_max_threads, ()) { return kRopeMaxBlocks * kRopeBlock; }
 // tokens == 0 returns 0 without a launch.
 TTDK_API(int, ttdk_rope, (const void* x, long long ldx, void* y, long long ldy, int dt, const float* table,
                           int table_rows, long long tokens, int S, int heads, int pos0, int inverse, hipStream_t st)) {
-  if (heads <= 0 || heads > (1 << 20) || S <= 0 || tokens < 0) return hipErrorInvalidValue;
-  if (tokens % S != 0) return hipErrorInvalidValue;
-  if (pos0 < 0 || static_cast<long long>(pos0) + S > table_rows) return hipErrorInvalidValue;
-  if (dt != 0 && dt != 1) return hipErrorInvalidValue;
-  const long long width = static_cast<long long>(heads) * 64;
-  if (ldx < width || ldy < width) return hipErrorInvalidValue;
-  const long long esz = dt == 0 ? 4 : 2;
-  if (!x || !y || !table || !aligned16(x) || !aligned16(y) || !aligned16(table)) return hipErrorInvalidValue;
-  if ((ldx * esz) % 16 != 0 || (ldy * esz) % 16 != 0) return hipErrorInvalidValue;
-  if (tokens == 0) return 0;
-  if (dt == 0) return rope_launch<float>(x, ldx, y, ldy, table, tokens, S, heads, pos0, inverse, st);
-  return rope_launch<bf16_t>(x, ldx, y, ldy, table, tokens, S, heads, pos0, inverse, st);
+  return rope_call<32>(x, ldx, y, ldy, dt, table, table_rows, tokens, S, heads, pos0, inverse, st);
+}
+
+// ttdk_rope for head size head_dim, 64 or 128 (anything else: hipErrorInvalidValue): heads*head_dim
+// columns are rotated, table is fp32 [table_rows][2][head_dim / 2]. Everything else as ttdk_rope.
+TTDK_API(int, ttdk_rope_hd, (const void* x, long long ldx, void* y, long long ldy, int dt, const float* table,
+                             int table_rows, long long tokens, int S, int heads, int head_dim, int pos0, int inverse,
+                             hipStream_t st)) {
+  if (head_dim == 64) return rope_call<32>(x, ldx, y, ldy, dt, table, table_rows, tokens, S, heads, pos0, inverse, st);
+  if (head_dim == 128) return rope_call<64>(x, ldx, y, ldy, dt, table, table_rows, tokens, S, heads, pos0, inverse, st);
+  return hipErrorInvalidValue;
 }

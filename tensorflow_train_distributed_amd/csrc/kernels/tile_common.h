@@ -42,6 +42,41 @@ __device__ __forceinline__ bf16x8_t rd_col(const char* lds, int r0, int r1, int 
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
+// ---- 128-element (256-B) rows: the images of the head_dim 128 kernels (attention128.hip).
+// A row is exactly the 64 banks x 4 B of the LDS, so the bank group (16 B, 4 banks) of a chunk is
+// its slot alone, whatever the row: the row parity that separates odd and even rows of a 128-B
+// image is gone, and off64's XOR would put rows r and r + 8 — and, in a column read, chunks c and
+// c + 1 of two rows — on the same slot. The slot here is
+//   chunk ^ sw(row),  sw(row) = ((row & 7) << 1) | ((row >> 3) & 1)    (16 values over 16 rows)
+// * b128 row read (rd_row128): the 16 lanes of a pass (16 x 16 B = 256 B) read rows r0 .. r0 + 15
+//   (r0 % 16 == 0) at one chunk c. sw runs over all 16 values, so c ^ sw(row) is 16 different
+//   slots: every bank once.
+// * ds_read_b64_tr_b16 column read (rd_col128): the 32 lanes of a pass (32 x 8 B = 256 B) read the 8
+//   rows r0 .. r0 + 7 (r0 % 8 == 0) at the two chunks c, c + 1 (c even), both 8-byte halves of
+//   each. Over the 8 rows sw = 2 j + a, j = 0..7, with one a = (row >> 3) & 1: bits 3..1 of
+//   c ^ sw take all 8 values with bit 0 = (c & 1) ^ a fixed, and c + 1 flips exactly bit 0 — the
+//   other 8 slots. 16 slots x 2 halves: every bank once.
+// * the loaders' b128 stores (16 lanes, one row, chunks 0..15): c ^ sw(row) is a permutation of c.
+// (Bank arithmetic on the 64-bank, 256 B / clk model that off64's measured conflict counts fit; the
+// 128-wide images have not been profiled.)
+__device__ __forceinline__ int off128(int row, int col) {  // byte offset of element (row, col), col % 4 == 0 ok
+  return row * 256 + (((col >> 3) ^ (((row & 7) << 1) | ((row >> 3) & 1))) << 4) + ((col & 7) << 1);
+}
+
+__device__ __forceinline__ bf16x8_t rd_row128(const char* lds, int row, int kchunk) {
+  return *reinterpret_cast<const bf16x8_t*>(lds + off128(row, kchunk * 8));
+}
+
+// rd_col of a [rows][128] image
+__device__ __forceinline__ bf16x8_t rd_col128(const char* lds, int r0, int r1, int colbase, int lane) {
+  const int i = lane & 15, g = lane >> 4, q = i >> 2, p = i & 3;
+  const s16x4_t lo = rd_tr(lds + off128(r0 + 4 * g + q, colbase + 4 * p));
+  const s16x4_t hi = rd_tr(lds + off128(r1 + 4 * g + q, colbase + 4 * p));
+  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
+  s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+
 __device__ __forceinline__ f32x4_t mfma(const bf16x8_t& x, const bf16x8_t& y, const f32x4_t& acc) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, y, acc, 0, 0, 0);
 }
@@ -74,6 +109,28 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
   const int xcd = bid & 7, idx = bid >> 3;
   const int q = nblocks >> 3, r = nblocks & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// Causal workgroups do unequal work (block b of a head streams 2b + 2 tiles in fwd / bwd_q, and
+// 2 (nblk - b) in bwd_kv), and the nblk blocks of a head stay adjacent in the grid (they share
+// K / V or Q / dO in one XCD's L2). Which block the j-th work item of head bh takes:
+//   order 0  natural (j);
+//   order 1  heavy first: the longest block of each head first. Measured no better than natural,
+//            and both about as slow as if every block were the longest: the grid then has period
+//            nblk, workgroups reach the CUs round-robin, so a CU keeps drawing the same block
+//            index and the CUs that draw the long one set the kernel's time;
+//   order 2  rotated: j plus the base-4 digit sum of bh. Over every power-of-two stride of the
+//            grid the block index then cycles evenly, so every CU gets the same mix.
+// (profiles/attn_causal_bench.txt)
+__device__ __forceinline__ int causal_block(int j, int bh, int nblk, int order, bool long_last) {
+  if (order == 2) {
+    uint32_t x = static_cast<uint32_t>(bh);
+    x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+    x = (x + (x >> 4)) & 0x0f0f0f0fu;
+    x = (x * 0x01010101u) >> 24;  // sum of the base-4 digits (<= 48)
+    return static_cast<int>((static_cast<uint32_t>(j) + x) % static_cast<uint32_t>(nblk));
+  }
+  return order == 1 && long_last ? nblk - 1 - j : j;
 }
 
 }  // namespace tile

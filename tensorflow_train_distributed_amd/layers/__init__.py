@@ -458,7 +458,9 @@ class Embedding(Layer):
 
 
 class MultiHeadAttention(Layer):
-    """Attention with fused QKV projection (head size 64 on the GPU flash kernels).
+    """Attention with fused QKV projection (key_dim 64 or 128 on the GPU flash kernels; 128 is the
+    head size of the LLaMA / Mistral / Qwen blocks, with every option below except window and
+    segment_ids, whose band kernels are 64-wide).
     call(x, value=None, seqlen=None, training=True, use_causal_mask=False): keys >= seqlen[b] are
     masked; use_causal_mask=True (Keras' name) lets position s attend positions <= s only, the
     decoder-only / left-to-right form.

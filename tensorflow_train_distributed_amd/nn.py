@@ -20,7 +20,7 @@ accumulation) for either input dtype.
     ttd.nn.conv2d(x, kernel, strides, padding)            # NHWC, kernel [R, S, C, K]
     ttd.nn.depthwise_conv2d(x, kernel, strides, padding, dilations)   # kernel [R, S, C, M], R, S <= 7
     ttd.nn.separable_conv2d(x, depthwise_kernel, pointwise_kernel)    # depthwise, then the 1x1 GEMM
-    ttd.nn.attention(q, k, v, num_heads, dropout_rate)    # [B, S, H*64] token-major
+    ttd.nn.attention(q, k, v, num_heads, dropout_rate)    # [B, S, H*64] or [B, S, H*128] token-major
     ttd.nn.attention(q, k, v, 16, num_kv_heads=4)         # grouped-query: k, v [B, Sk, 4*64]
     ttd.nn.rotary_embedding(q, 16, offset=0)              # RoPE on q / k before attention
     ttd.nn.rms_norm(x, gamma); ttd.nn.swiglu(x)           # RMSNorm; silu(x[..., :I]) * x[..., I:]
@@ -950,7 +950,8 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, q, k, v, num_heads, rate, seqlen, site, causal, num_kv_heads, band=None):
         from .ops import transformer as T
         B, S, D = q.shape
-        Sk, Dk = k.shape[1], k.shape[2]  # Dk = num_kv_heads * 64: narrower than D when heads are grouped
+        Sk, Dk = k.shape[1], k.shape[2]  # Dk = num_kv_heads * head_dim: narrower than D when heads are grouped
+        hd = D // num_heads  # 64 or 128 (checked by attention)
         q2 = q.reshape(B * S, D).to(torch.bfloat16).contiguous()
         k2, v2 = [t.reshape(B * Sk, Dk).to(torch.bfloat16).contiguous() for t in (k, v)]
         o = torch.empty_like(q2)
@@ -963,20 +964,20 @@ class _Attention(torch.autograd.Function):
         if band is not None:  # seqlen and causal are in the table
             seqlen, causal = None, False
         T.attention_fwd(q2, k2, v2, o, lse, B, num_heads, S, Sk=Sk, Hk=num_kv_heads, seqlen=seqlen, p_drop=rate,
-                        rng=rng, site=site, causal=causal, band=band)
+                        rng=rng, site=site, causal=causal, band=band, head_dim=hd)
         ctx.save_for_backward(q2, k2, v2, o, lse, seqlen, band)
-        ctx.cfg = (B, S, Sk, D, Dk, num_heads, num_kv_heads, rate, rng, site, q.dtype, causal)
+        ctx.cfg = (B, S, Sk, D, Dk, num_heads, num_kv_heads, rate, rng, site, q.dtype, causal, hd)
         return o.reshape(B, S, D).to(q.dtype)
 
     @staticmethod
     def backward(ctx, do):
         from .ops import transformer as T
         q2, k2, v2, o, lse, seqlen, band = ctx.saved_tensors
-        B, S, Sk, D, Dk, nh, nkv, rate, rng, site, dt, causal = ctx.cfg
+        B, S, Sk, D, Dk, nh, nkv, rate, rng, site, dt, causal, hd = ctx.cfg
         d2 = do.reshape(B * S, D).to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2)
         T.attention_bwd(q2, k2, v2, o, d2, lse, dq, dk, dv, B, nh, S, Sk=Sk, Hk=nkv, seqlen=seqlen, p_drop=rate,
-                        rng=rng, site=site, causal=causal, band=band)
+                        rng=rng, site=site, causal=causal, band=band, head_dim=hd)
         return (dq.reshape(B, S, D).to(dt), dk.reshape(B, Sk, Dk).to(dt), dv.reshape(B, Sk, Dk).to(dt),
                 None, None, None, None, None, None, None)
 
@@ -1008,19 +1009,19 @@ def attention_band_mask(segment_ids, seqlen, window, causal, B, S, device):
 
 def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, site: int = 0, causal: bool = False,
               num_kv_heads: Optional[int] = None, segment_ids=None, window=None):
-    """Multi-head scaled dot-product attention, token-major inputs: q [B, S, num_heads*64], k and v
-    [B, Sk, num_kv_heads*64]. Sk == S is self-attention; Sk != S is cross-attention over a memory of
+    """Multi-head scaled dot-product attention, token-major inputs: q [B, S, num_heads*head_dim], k and
+    v [B, Sk, num_kv_heads*head_dim]. Sk == S is self-attention; Sk != S is cross-attention over a memory of
     another length (a decoder's attention over the encoder's output): the result has the query's
     S rows, the gradients of k and v have Sk rows. Keys >= seqlen[b] are masked — seqlen is the
     keys' (the memory's) valid length, at most Sk; queries are never masked. causal=True also masks
     keys after the query (position s attends positions <= s: a left-to-right language model) and
-    needs Sk == S. GPU: the flash kernels (head_dim 64, S % 128 == 0 and Sk % 128 == 0); their
+    needs Sk == S. GPU: the flash kernels (head_dim 64 or 128, S % 128 == 0 and Sk % 128 == 0); their
     causal form skips the key tiles above the diagonal.
     num_kv_heads (None: num_heads) is grouped-query attention, num_kv_heads=1 multi-query attention:
     num_heads % num_kv_heads == 0 and query head h attends key/value head h // (num_heads //
     num_kv_heads) — the heads of a group are contiguous, as torch.repeat_interleave over the head
     axis lays them out. k and v are never repeated in memory, and their gradients come back
-    num_kv_heads*64 wide, each key/value head the sum over the query heads of its group.
+    num_kv_heads*head_dim wide, each key/value head the sum over the query heads of its group.
     Banded masks (self-attention only; they intersect with each other, with causal and with seqlen):
     segment_ids int32 [B, S] packs several documents into a row — a token attends the tokens of its
     own maximal run of equal ids (an id that reappears later in the row is another document); a
@@ -1029,7 +1030,8 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
     q - left <= k <= q + right, None on a side for no bound; causal=True clamps right to 0. A row
     whose intersection is empty behaves like a padding row. GPU: the table of
     ops.transformer.attention_band and the BAND kernels, which stream only the key tiles of each
-    block's range; CPU: the same mask on the fp32 formulas (zero rows, not NaN). With
+    block's range — head_dim 64 only: with head_dim 128 segment_ids / window raise on the GPU; CPU:
+    the same mask on the fp32 formulas (zero rows, not NaN). With
     segment_ids=None and no bound in window the call takes exactly the path it took without them."""
     from .ops import transformer as T
     B, S, D = q.shape
@@ -1059,11 +1061,15 @@ def attention(q, k, v, num_heads: int, dropout_rate: float = 0.0, seqlen=None, s
             raise InvalidArgumentError("ttd.nn.attention: segment_ids must be int32 [batch, seq_len] = [%d, %d], got "
                                        "%s %s" % (B, S, segment_ids.dtype, tuple(segment_ids.shape)))
     if _on_gpu(q, k, v):
-        if hd != 64 or S % 128 != 0 or Sk % 128 != 0 or D % num_heads:
+        if hd not in (64, 128) or S % 128 != 0 or Sk % 128 != 0 or D % num_heads:
             raise InvalidArgumentError(
-                "ttd.nn.attention on GPU runs the flash kernels for head_dim 64 and seq_len %% 128 == 0 "
-                "(got head_dim %s, seq_len %d%s); pad the sequence (and mask it with seqlen) or use 64-wide heads"
-                % (D / num_heads, S, "" if Sk == S else ", key seq_len %d" % Sk))
+                "ttd.nn.attention on GPU runs the flash kernels for head_dim 64 or 128 and seq_len %% 128 == 0 "
+                "(got head_dim %s, seq_len %d%s); pad the sequence (and mask it with seqlen) or use 64- or "
+                "128-wide heads" % (D / num_heads, S, "" if Sk == S else ", key seq_len %d" % Sk))
+        if banded and hd != 64:
+            raise InvalidArgumentError(
+                "ttd.nn.attention on GPU: segment_ids / window run the band kernels, which are 64-wide "
+                "(got head_dim %d); use 64-wide heads for banded masks" % hd)
         sl = seqlen.to(torch.int32).contiguous() if seqlen is not None else None
         if banded:
             ids = segment_ids.to(q.device).contiguous() if segment_ids is not None else None
@@ -1117,7 +1123,7 @@ class _Rotary(torch.autograd.Function):
         from .ops import transformer as T
         B, S, D = x.shape
         y = torch.empty((B * S, D), dtype=x.dtype, device=x.device)
-        T.rope(_token_rows(x, B, S, D), y, table, S, num_heads, pos0=offset)
+        T.rope(_token_rows(x, B, S, D), y, table, S, num_heads, pos0=offset, head_dim=D // num_heads)
         ctx.cfg = (num_heads, table, offset)
         return y.view(B, S, D)
 
@@ -1127,7 +1133,7 @@ class _Rotary(torch.autograd.Function):
         num_heads, table, offset = ctx.cfg
         B, S, D = dy.shape
         dx = torch.empty((B * S, D), dtype=dy.dtype, device=dy.device)
-        T.rope(_token_rows(dy, B, S, D), dx, table, S, num_heads, pos0=offset, inverse=True)
+        T.rope(_token_rows(dy, B, S, D), dx, table, S, num_heads, pos0=offset, inverse=True, head_dim=D // num_heads)
         return dx.view(B, S, D), None, None, None
 
 
@@ -1140,7 +1146,7 @@ def rotary_embedding(x, num_heads: int, base: float = 10000.0, offset: int = 0):
     Apply it to q and k before attention (`offset`: the position of the first token, e.g. the
     length of a cached prefix). The result has x's shape and dtype; the backward is the inverse
     rotation of the incoming gradient (the rotation is orthogonal), the same kernel with -sin.
-    GPU: head_dim 64 only, any S; bf16 stays bf16 and fp32 stays fp32 (rope.hip, cos / sin from a
+    GPU: head_dim 64 or 128, any S; bf16 stays bf16 and fp32 stays fp32 (rope.hip, cos / sin from a
     host-built table: ops.transformer.rope_table, offset + S rows rounded up to a power of two, at
     least 512). A view with unit column stride and uniformly strided rows — a column slice of a
     fused projection — is read through its row stride without a copy. CPU: the same convention in
@@ -1161,15 +1167,15 @@ def rotary_embedding(x, num_heads: int, base: float = 10000.0, offset: int = 0):
     if offset < 0:
         raise InvalidArgumentError("ttd.nn.rotary_embedding: offset must be >= 0 (got %d)" % offset)
     if _on_gpu(x):
-        if hd != 64:
+        if hd not in (64, 128):
             raise InvalidArgumentError(
-                "ttd.nn.rotary_embedding on GPU runs the rotary kernel for head_dim 64 (got head_dim %d); "
-                "use 64-wide heads" % hd)
+                "ttd.nn.rotary_embedding on GPU runs the rotary kernel for head_dim 64 or 128 (got head_dim %d); "
+                "use 64- or 128-wide heads" % hd)
         from .ops import transformer as T
         rows = max(512, 1 << (offset + S - 1).bit_length())
         if B * S == 0:
             return x.clone()
-        return _Rotary.apply(x, num_heads, T.rope_table(rows, base, x.device), offset)
+        return _Rotary.apply(x, num_heads, T.rope_table(rows, base, x.device, head_dim=hd), offset)
     half = hd // 2
     pos = torch.arange(offset, offset + S, dtype=torch.float64)
     ang = pos[:, None] * float(base) ** (-torch.arange(half, dtype=torch.float64) / half)

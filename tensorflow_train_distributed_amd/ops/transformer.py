@@ -1,4 +1,4 @@
-"""Launch wrappers for the transformer kernels (attention.hip, transformer.hip, rope.hip,
+"""Launch wrappers for the transformer kernels (attention.hip, attention128.hip, transformer.hip, rope.hip,
 rmsnorm_glu.hip) plus exact
 CPU re-implementations of their dropout hash (used by the numerics tests as oracles).
 
@@ -162,10 +162,22 @@ def _band_arg(band, B, S, Sk, causal, seqlen):
                                    "pass them there, not beside band=")
 
 
+def _attn_exports(head_dim, band):
+    """(forward, backward) export names for a head size: 64 (attention.hip) or 128 (attention128.hip,
+    same argument lists; no band form)."""
+    if head_dim == 64:
+        return "ttdk_attn_fwd", "ttdk_attn_bwd"
+    if head_dim != 128:
+        raise InvalidArgumentError("attention: the flash kernels serve head_dim 64 and 128 (got %r)" % (head_dim,))
+    if band is not None:
+        raise InvalidArgumentError("attention band: the band kernels are 64-wide; head_dim 128 has no band form")
+    return "ttdk_attn128_fwd", "ttdk_attn128_bwd"
+
+
 def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, p_drop=0.0, rng=None, site=0,
-                  causal=False, band=None):
-    """q/out: 2-D bf16 views [B*S, >= H*64], k/v: [B*Sk, >= Hk*64] (row stride = .stride(0), each its
-    own); lse fp32 [B*H, S]. Sk (None: S) is the key length — cross-attention over a memory of
+                  causal=False, band=None, head_dim=64):
+    """q/out: 2-D bf16 views [B*S, >= H*head_dim], k/v: [B*Sk, >= Hk*head_dim] (row stride =
+    .stride(0), each its own), head_dim 64 or 128; lse fp32 [B*H, S]. Sk (None: S) is the key length — cross-attention over a memory of
     another length; seqlen then holds the memory's valid lengths (keys >= seqlen[b] masked).
     causal: query s attends keys <= s only (combined with seqlen); the key tiles above the diagonal
     are not streamed. causal needs Sk == S.
@@ -175,7 +187,8 @@ def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, 
     band (a table of attention_band) runs the BAND kernels: each query row attends the key range the
     table gives it (documents, windows, causal and seqlen, all folded into the table — so seqlen
     and causal are not passed beside it), and key tiles outside a block's range are not streamed.
-    Self-attention only: a band with Sk != S raises."""
+    Self-attention only: a band with Sk != S raises, and so does a band with head_dim=128."""
+    fwd, _ = _attn_exports(head_dim, band)
     if band is not None:
         _band_arg(band, B, S, Sk, causal, seqlen)
         _lib.call("ttdk_attn_band_fwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
@@ -183,7 +196,7 @@ def attention_fwd(q, k, v, out, lse, B, H, S, *, Sk=None, Hk=None, seqlen=None, 
                   int(H if Hk is None else Hk), S, S, float(p_drop), _p(rng.t if rng is not None else None),
                   int(site), _s())
         return out, lse
-    _lib.call("ttdk_attn_fwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+    _lib.call(fwd, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
               out.data_ptr(), out.stride(0), lse.data_ptr(), _p(seqlen), B, H, int(H if Hk is None else Hk), S,
               int(S if Sk is None else Sk), float(p_drop), _p(rng.t if rng is not None else None), int(site),
               int(bool(causal)), _s())
@@ -195,18 +208,21 @@ def set_fused_attention_bwd(on: bool):
     at BERT-Large: attention.hip) or the split dQ / dK-dV kernels (default;
     TTD_ATTN_FUSED_BWD=1 at start-up selects the fused one). A causal backward ignores the switch:
     the fused kernel has no causal form, so attention_bwd(..., causal=True) always runs the split
-    kernels; so does a cross-attention backward (Sk != S) and a grouped-query one (Hk != H)."""
+    kernels; so does a cross-attention backward (Sk != S), a grouped-query one (Hk != H) and every
+    head_dim 128 backward (the fused kernel is 64-wide)."""
     _lib.call("ttdk_attn_set_fused_bwd", int(bool(on)))
 
 
 def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=None, delta=None, seqlen=None,
-                  p_drop=0.0, rng=None, site=0, causal=False, band=None):
-    """Backward of attention_fwd with the same Sk / Hk / seqlen / p_drop / rng / site / causal / band.
+                  p_drop=0.0, rng=None, site=0, causal=False, band=None, head_dim=64):
+    """Backward of attention_fwd with the same Sk / Hk / seqlen / p_drop / rng / site / causal / band /
+    head_dim (128: always the split kernels of attention128.hip).
     dq has the query's B*S rows, dk / dv the keys' B*Sk; delta fp32 [B*H, S]. Sk != S always runs the
     split kernels (the fused backward is a self-attention kernel), and so does Hk != H: dk / dv then
-    have Hk*64 columns, each key/value head the sum over its H // Hk query heads — summed in fp32
+    have Hk*head_dim columns, each key/value head the sum over its H // Hk query heads — summed in fp32
     registers in head order (deterministic), rounded to bf16 once. A band backward always runs the
     split kernels too (the fused backward has no band form)."""
+    _, bwd = _attn_exports(head_dim, band)
     if delta is None:
         delta = torch.empty((B * H, S), dtype=torch.float32, device=q.device)
     if band is not None:
@@ -217,7 +233,7 @@ def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=Non
                   dv.stride(0), band.data_ptr(), B, H, int(H if Hk is None else Hk), S, S, float(p_drop),
                   _p(rng.t if rng is not None else None), int(site), _s())
         return dq, dk, dv
-    _lib.call("ttdk_attn_bwd", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+    _lib.call(bwd, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
               o.data_ptr(), o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(), delta.data_ptr(),
               dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), _p(seqlen),
               B, H, int(H if Hk is None else Hk), S, int(S if Sk is None else Sk), float(p_drop),
@@ -227,19 +243,23 @@ def attention_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, S, *, Sk=None, Hk=Non
 
 # ------------------------------------------------------------------ rotary position embeddings
 _ROPE_DT = {torch.float32: 0, torch.bfloat16: 1}
-_rope_tables = {}  # (device, base, rows) -> table; never evicted (a captured hipGraph may hold the pointer)
+_rope_tables = {}  # (device, base, rows, head_dim) -> table; never evicted (a captured hipGraph may hold the pointer)
 
 
-def rope_table(rows, base=10000.0, device="cuda"):
-    """fp32 [rows, 2, 32] table of the rotary embedding (rope.hip): [p, 0, i] = cos(p * base**(-i/32)),
+def rope_table(rows, base=10000.0, device="cuda", head_dim=64):
+    """fp32 [rows, 2, half] table of the rotary embedding (rope.hip), half = head_dim / 2 (head_dim 64
+    or 128): [p, 0, i] = cos(p * base**(-i/half)),
     [p, 1, i] the sine, computed on the host in float64 and rounded once to fp32. Cached per
-    (device, base, rows) and never evicted, because a captured hipGraph may hold the pointer; a
+    (device, base, rows, head_dim) and never evicted, because a captured hipGraph may hold the pointer; a
     cache miss while the current stream is capturing raises instead of copying inside the capture
     (build the table before the capture). A CPU device gives the same table."""
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    key = (str(dev), float(base), int(rows))
+    if head_dim not in (64, 128):
+        raise InvalidArgumentError("rope_table: the rotary kernel serves head_dim 64 and 128 (got %r)" % (head_dim,))
+    half = head_dim // 2
+    key = (str(dev), float(base), int(rows), int(head_dim))
     t = _rope_tables.get(key)
     if t is None:
         if rows <= 0 or not base > 0:
@@ -248,25 +268,31 @@ def rope_table(rows, base=10000.0, device="cuda"):
             raise RuntimeError(
                 "rope_table(%d, base=%r) is not cached and the current stream is capturing a graph: the table's "
                 "host-to-device copy cannot run inside a capture; build the table before the capture" % (rows, base))
-        ang = np.arange(int(rows), dtype=np.float64)[:, None] * float(base) ** (-np.arange(32, dtype=np.float64) / 32.0)
+        ang = np.arange(int(rows), dtype=np.float64)[:, None] * float(base) ** (-np.arange(half, dtype=np.float64) / half)
         t = torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)).to(dev)
         _rope_tables[key] = t
     return t
 
 
-def rope(x, y, table, S, heads, *, pos0=0, inverse=False):
-    """y[r, :heads*64] = the half-split rotation of x[r, :heads*64] at position pos0 + r % S
-    (inverse=True: the inverse rotation, which is also the backward). x, y: 2-D views [tokens,
-    >= heads*64] of one dtype (bf16 or fp32) with unit column stride, each with its own row stride;
-    columns from heads*64 on are not touched. y may be x (in place, e.g. x = qkv with heads =
+def rope(x, y, table, S, heads, *, pos0=0, inverse=False, head_dim=64):
+    """y[r, :heads*head_dim] = the half-split rotation of x[r, :heads*head_dim] at position pos0 + r % S
+    (inverse=True: the inverse rotation, which is also the backward), head_dim 64 or 128. x, y: 2-D
+    views [tokens, >= heads*head_dim] of one dtype (bf16 or fp32) with unit column stride, each with
+    its own row stride; columns from heads*head_dim on are not touched. y may be x (in place, e.g. x = qkv with heads =
     H + Hk rotates q and k of the fused projection in one launch); any other overlap of x and y is
-    the caller's error. table: rope_table(rows >= pos0 + S) on x's device."""
+    the caller's error. table: rope_table(rows >= pos0 + S, head_dim=head_dim) on x's device."""
     if x.dtype != y.dtype or x.dtype not in _ROPE_DT or x.dim() != 2 or y.shape[0] != x.shape[0] \
-            or x.stride(1) != 1 or y.stride(1) != 1 or table.dtype != torch.float32 or not table.is_contiguous():
+            or x.stride(1) != 1 or y.stride(1) != 1 or table.dtype != torch.float32 or not table.is_contiguous() \
+            or head_dim not in (64, 128) or tuple(table.shape[1:]) != (2, head_dim // 2):
         raise _lib.HipKernelError("rope: x and y must be 2-D bf16 or fp32 views of one dtype and row count with unit "
-                                  "column stride, table contiguous fp32")
-    _lib.call("ttdk_rope", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _ROPE_DT[x.dtype],
-              table.data_ptr(), table.shape[0], x.shape[0], int(S), int(heads), int(pos0), int(bool(inverse)), _s())
+                                  "column stride, head_dim 64 or 128, table contiguous fp32 [rows, 2, head_dim / 2]")
+    if head_dim == 64:
+        _lib.call("ttdk_rope", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _ROPE_DT[x.dtype],
+                  table.data_ptr(), table.shape[0], x.shape[0], int(S), int(heads), int(pos0), int(bool(inverse)), _s())
+    else:
+        _lib.call("ttdk_rope_hd", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _ROPE_DT[x.dtype],
+                  table.data_ptr(), table.shape[0], x.shape[0], int(S), int(heads), int(head_dim), int(pos0),
+                  int(bool(inverse)), _s())
     return y
 
 

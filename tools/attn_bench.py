@@ -14,7 +14,12 @@ for no bound), --segments N with N equal documents per row (N = 1: the band form
 masked, against the plain kernels); both combine with each other, --causal and --kv-heads. The
 line then also gives the time of the table kernel (ttdk_attn_band) and the share of the dense
 64 x 64 tiles the forward streams; TF/s stay dense-equivalent. --seq S sets the sequence length.
-usage: python tools/attn_bench.py [B] [--causal | --kv-seq N] [--kv-heads N] [--window L,R] [--segments N] [--seq S]"""
+--head-dim 128 times the 128-wide kernels (attention128.hip: split backward only, no band form) and
+--heads H sets the number of query heads (16): H = 16 at 128 beside H = 32 at 64 is the same matrix
+FLOPs (profiles/attn_hd128_bench.txt; the per-kernel split of the backward there is a kernel trace
+of this script). --iters N sets the calls per timed window (20).
+usage: python tools/attn_bench.py [B] [--causal | --kv-seq N] [--kv-heads N] [--window L,R] [--segments N] [--seq S]
+                                  [--head-dim D] [--heads H] [--iters N]"""
 import sys
 
 import torch
@@ -23,7 +28,11 @@ sys.path.insert(0, ".")
 from tensorflow_train_distributed_amd.ops import transformer as T  # noqa: E402
 
 
-def timeit(fn, iters=20):
+ITERS = 20
+
+
+def timeit(fn, iters=None):
+    iters = iters or ITERS
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -61,7 +70,22 @@ if "--seq" in argv:
     i = argv.index("--seq")
     S_arg = int(argv[i + 1])
     del argv[i:i + 2]
+H_arg, D_arg = 16, 64
+if "--iters" in argv:
+    i = argv.index("--iters")
+    ITERS = int(argv[i + 1])
+    del argv[i:i + 2]
+if "--heads" in argv:
+    i = argv.index("--heads")
+    H_arg = int(argv[i + 1])
+    del argv[i:i + 2]
+if "--head-dim" in argv:
+    i = argv.index("--head-dim")
+    D_arg = int(argv[i + 1])
+    del argv[i:i + 2]
 banded = window is not None or segments is not None
+if banded and D_arg != 64:
+    sys.exit("--window / --segments need --head-dim 64: the band kernels are 64-wide")
 if banded and Sk is not None:
     sys.exit("--window / --segments and --kv-seq exclude each other: a band is a self-attention mask")
 args = [a for a in argv if not a.startswith("--")]
@@ -70,7 +94,7 @@ if causal and Sk is not None:
     sys.exit("--causal and --kv-seq exclude each other: the causal kernels need Sk == S")
 if Hk is not None and Sk is not None:
     sys.exit("--kv-heads and --kv-seq exclude each other")
-B, H, S, D = (int(args[0]) if args else 32), 16, S_arg, 64
+B, H, S, D = (int(args[0]) if args else 32), H_arg, S_arg, D_arg
 if Hk is not None and (Hk <= 0 or H % Hk):
     sys.exit("--kv-heads must divide %d" % H)
 # one label, one buffer layout per mode; everything below is shared
@@ -80,6 +104,8 @@ elif Hk is not None:
     label = "%skv-heads %2d " % ("causal " if causal else "", Hk)
 else:
     label = "causal " if causal else ""
+if (H, D) != (16, 64):
+    label += "H=%d d=%d " % (H, D)
 if banded:
     label += "band%s%s " % ("" if window is None else " window %s,%s" % window,
                             "" if segments is None else " %d docs" % segments)
@@ -112,13 +138,13 @@ if banded:
     share = float((blk[..., 1] - blk[..., 0]).sum()) / (B * (S // 128) * (S // 64))
     band_note = "   table %5.1f us, fwd streams %4.1f %% of the tiles" % (tband, 100 * share)
 for p in (0.0, 0.1):
-    kw = dict(Sk=Sk, Hk=Hk, p_drop=p, rng=rng, causal=causal)
+    kw = dict(Sk=Sk, Hk=Hk, p_drop=p, rng=rng, causal=causal, head_dim=D)
     if banded:  # causal is in the table
         kw = dict(Hk=Hk, p_drop=p, rng=rng, band=band)
     tf = timeit(lambda: T.attention_fwd(q, k, v, out, lse, B, H, S, **kw))
     line = "%sp=%.1f  fwd %6.1f us %5.0f TF/s   bwd" % (label, p, tf, fl / tf / 1e6)
     # the fused backward has a self-attention, non-causal form only
-    for fused in ((True, False) if label == "" else (False,)):
+    for fused in ((True, False) if label == "" else (False,)):  # (label == "": plain 64-wide self-attention)
         T.set_fused_attention_bwd(fused)
         tb = timeit(lambda: T.attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, S, delta=delta, **kw))
         line += " %s %6.1f us %5.0f TF/s  " % ("fused" if fused else "split", tb, 2.5 * fl / tb / 1e6)
