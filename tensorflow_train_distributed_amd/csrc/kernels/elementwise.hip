@@ -258,7 +258,10 @@ __device__ __forceinline__ float act_grad(float z, int act) {
       const float k0 = 0.7978845608028654f, k1 = 0.044715f;
       const float u = k0 * (z + k1 * z * z * z);
       const float t = tanhf(u);
-      return 0.5f * (1.f + t) + 0.5f * z * (1.f - t * t) * k0 * (1.f + 3.f * k1 * z * z);
+      // Past |z| ~ 1.8e19 the polynomial overflows while 1 - t*t is long 0 (t is +-1 from |z| ~ 5
+      // on): kept finite, the second term is 0 there and not 0 * inf = NaN (the derivative is 1 or 0).
+      const float p = fminf(1.f + 3.f * k1 * z * z, 3.0e38f);
+      return 0.5f * (1.f + t) + 0.5f * z * (1.f - t * t) * k0 * p;
     }
     case kElu: return z > 0.f ? 1.f : expf(z);
     default: return 1.f;
@@ -613,6 +616,7 @@ static void colsum_plan(long long rows, int C, int dtype, bool vec, long long* s
   }
   if (sl < 1) sl = 1;
   *per = (rows + sl - 1) / sl;
+  if (*per < 1) *per = 1;  // rows == 0: one empty slice (out = beta ? out : 0), no workspace
   *slices = (rows + *per - 1) / *per;
   if (*slices < 1) *slices = 1;
 }
