@@ -116,7 +116,8 @@ def hip_sources():
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"],
                "attention128.hip": ["-fno-slp-vectorize", *_NO_PK_F32],
-               "rope.hip": _NO_PK_F32}
+               "rope.hip": _NO_PK_F32,
+               "grouped_gemm.hip": _NO_PK_F32}
 
 
 def build_hip(force: bool = False) -> str:

@@ -441,6 +441,80 @@ class SwiGLU(Layer):
         return N.swiglu(N.dense(x, self.kernel, self.bias))
 
 
+class _Gather(torch.autograd.Function):
+    """src[idx // k] for a permutation idx of the src.shape[0] * k slots, with the inverse
+    permutation handed in: the gradient is d[inv] summed over each row's k slots, a gather too, so
+    neither direction scatters (no index_add, deterministic)."""
+
+    @staticmethod
+    def forward(ctx, src, idx, inv, k):
+        ctx.save_for_backward(inv)
+        ctx.k = k
+        return src[idx // k if k > 1 else idx]
+
+    @staticmethod
+    def backward(ctx, d):
+        (inv,) = ctx.saved_tensors
+        g = d[inv]
+        return (g.reshape(-1, ctx.k, g.shape[-1]).sum(1) if ctx.k > 1 else g), None, None, None
+
+
+class MixtureOfExperts(Layer):
+    """Token-choice mixture-of-experts feed-forward over the last axis (Mixtral / Qwen-MoE block):
+    an fp32 router (`router/kernel` [in, num_experts], no bias), softmax, top_k experts per token
+    with their probabilities renormalised to sum 1, and per expert a feed-forward of width
+    intermediate_size — gated: swiglu(x W_in) W_out with `experts_in/kernel` [E, in, 2 * F] (gate
+    columns first); not gated: gelu(x W_in) W_out with [E, in, F] — `experts_out/kernel` [E, F, in].
+    Tokens are sorted by expert on the device and both projections are one grouped matmul
+    (ttd.nn.grouped_matmul); nothing here reads the routing back to the host, no token is dropped.
+    `aux_loss` holds the Switch load-balancing term of the last call, E * sum_e f_e * P_e with f_e
+    the share of the tokens' top_k slots routed to expert e and P_e the mean router probability
+    of e; like `losses` it is part of no loss unless the caller adds it."""
+    _default_name = "mixture_of_experts"
+
+    def __init__(self, num_experts, top_k, intermediate_size, gated=True, kernel_initializer="glorot_uniform",
+                 kernel_regularizer=None, name=None, trainable=True):
+        super().__init__(name, trainable)
+        self.num_experts, self.top_k, self.intermediate_size = int(num_experts), int(top_k), int(intermediate_size)
+        self.gated = bool(gated)
+        if self.num_experts < 1 or not 1 <= self.top_k <= self.num_experts or self.intermediate_size < 1:
+            raise InvalidArgumentError("MixtureOfExperts: need num_experts >= 1, 1 <= top_k <= num_experts and a "
+                                       "positive intermediate_size, got %d, %d, %d"
+                                       % (self.num_experts, self.top_k, self.intermediate_size))
+        self.kernel_initializer, self.kernel_regularizer = kernel_initializer, kernel_regularizer
+        self.aux_loss = None
+
+    def build(self, input_shape):
+        D, E, Fi = input_shape[-1], self.num_experts, self.intermediate_size
+        init = I.get(self.kernel_initializer)
+
+        def per_expert(shape, gen):  # every expert's [in, out] slice drawn as a Dense kernel of that shape
+            return torch.stack([init(tuple(shape[1:]), gen) for _ in range(shape[0])])
+
+        self.add_weight("router/kernel", (D, E), self.kernel_initializer, self.kernel_regularizer)
+        self.add_weight("experts_in/kernel", (E, D, (2 if self.gated else 1) * Fi), per_expert, self.kernel_regularizer)
+        self.add_weight("experts_out/kernel", (E, Fi, D), per_expert, self.kernel_regularizer)
+        super().build(input_shape)
+
+    def call(self, x, **kw):
+        E, k = self.num_experts, self.top_k
+        x2 = x.reshape(-1, x.shape[-1])
+        T = x2.shape[0]
+        probs = torch.softmax(N.dense(x2.float(), self.router_kernel.float()), dim=-1)   # [T, E]
+        gate, expert = torch.topk(probs, k, dim=-1)
+        gate = gate / gate.sum(-1, keepdim=True)
+        slots = expert.reshape(-1)                        # slot t * k + j: the j-th expert of token t
+        order = torch.argsort(slots, stable=True)         # sorted row -> slot
+        inv = torch.argsort(order)                        # slot -> sorted row
+        sizes = torch.bincount(slots, minlength=E)
+        self.aux_loss = E * torch.sum(sizes.to(probs.dtype) / (T * k) * probs.mean(0))
+        h = N.grouped_matmul(_Gather.apply(x2, order, inv, k), self.experts_in_kernel, sizes)
+        h = N.swiglu(h) if self.gated else N.gelu(h)
+        h = N.grouped_matmul(h, self.experts_out_kernel, sizes)
+        y = (_Gather.apply(h, inv, order, 1).reshape(T, k, -1).float() * gate.unsqueeze(-1)).sum(1)
+        return y.to(x.dtype).reshape(x.shape)
+
+
 class Embedding(Layer):
     _default_name = "embedding"
 

@@ -25,6 +25,7 @@ accumulation) for either input dtype.
     ttd.nn.rotary_embedding(q, 16, offset=0)              # RoPE on q / k before attention
     ttd.nn.rms_norm(x, gamma); ttd.nn.swiglu(x)           # RMSNorm; silu(x[..., :I]) * x[..., I:]
     ttd.nn.group_norm(x, gamma, beta, groups=32)          # [N, *spatial, C], per-sample group statistics
+    ttd.nn.grouped_matmul(x, kernels, group_sizes)        # rows sorted by expert, kernels [E, K, N]
 """
 from __future__ import annotations
 
@@ -624,6 +625,60 @@ def swiglu(x):
         return _SwiGLU.apply(x)
     a, b = x.chunk(2, dim=-1)
     return F.silu(a) * b
+
+
+class _GroupedMatMul(torch.autograd.Function):
+    """One launch each for y, dx and dw of a grouped matmul (grouped_gemm.hip; dx on a transposed
+    copy of the weights). The group offsets are formed and read on the device: no host sync, so
+    the op can be captured into a graph."""
+
+    @staticmethod
+    def forward(ctx, x, kernels, group_sizes):
+        from .ops import gemm as G
+        xb = x.to(torch.bfloat16).contiguous()
+        wb = kernels.to(torch.bfloat16).contiguous()          # [E, in, out]
+        off = F.pad(torch.cumsum(group_sizes, 0, dtype=torch.int32), (1, 0))
+        y = G.grouped_gemm(xb, wb, off)
+        ctx.save_for_backward(xb, wb, off)
+        ctx.cfg = (x.dtype, kernels.dtype)
+        return y.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import gemm as G
+        xb, wb, off = ctx.saved_tensors
+        xdt, wdt = ctx.cfg
+        d = dy.to(torch.bfloat16).contiguous()
+        dx = G.grouped_gemm(d, wb.transpose(1, 2).contiguous(), off).to(xdt) if ctx.needs_input_grad[0] else None
+        dw = G.grouped_wgrad(xb, d, off).to(wdt) if ctx.needs_input_grad[1] else None
+        return dx, dw, None
+
+
+def grouped_matmul(x, kernels, group_sizes):
+    """y[r] = x[r] @ kernels[e] for the rows r of group e: x [M, K] sorted by group, kernels
+    [E, K, N], group_sizes an integer tensor [E] on x's device (group e owns the group_sizes[e] rows
+    after those of groups < e). Rows past group_sizes.sum() give zero output and zero gradient. The
+    expert matmul of a mixture-of-experts block. GPU: the grouped MFMA kernels in bf16 with fp32
+    accumulation, K and N multiples of 8; CPU: a loop over the groups in the input dtype."""
+    if x.dim() != 2 or kernels.dim() != 3 or kernels.shape[1] != x.shape[1]:
+        raise InvalidArgumentError("ttd.nn.grouped_matmul: x must be [M, K] and kernels [E, K, N], got %s and %s"
+                                   % (tuple(x.shape), tuple(kernels.shape)))
+    E = kernels.shape[0]
+    if (group_sizes.is_floating_point() or group_sizes.is_complex() or group_sizes.dtype == torch.bool
+            or tuple(group_sizes.shape) != (E,) or group_sizes.device != x.device):
+        raise InvalidArgumentError("ttd.nn.grouped_matmul: group_sizes must be an integer [%d] tensor on %s, got %s %s "
+                                   "on %s" % (E, x.device, group_sizes.dtype, tuple(group_sizes.shape),
+                                              group_sizes.device))
+    if _on_gpu(x, kernels):
+        return _GroupedMatMul.apply(x, kernels, group_sizes)
+    outs, r = [], 0
+    for e, m in enumerate(group_sizes.tolist()):
+        outs.append(x[r:r + m] @ kernels[e])
+        r += m
+    if r > x.shape[0]:
+        raise InvalidArgumentError("ttd.nn.grouped_matmul: group_sizes sum to %d, x has %d rows" % (r, x.shape[0]))
+    outs.append(x.new_zeros((x.shape[0] - r, kernels.shape[2])))
+    return torch.cat(outs)
 
 
 class _BatchNorm(torch.autograd.Function):

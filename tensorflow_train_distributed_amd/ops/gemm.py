@@ -11,6 +11,7 @@ import ctypes
 import torch
 
 from . import _lib, _plan
+from ..utils.errors import InvalidArgumentError
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH, ACT_DGELU = 0, 1, 2, 3, 4
 
@@ -206,6 +207,84 @@ def gemm_batched(a, b, *, trans_a=False, trans_b=False, out_dtype=torch.float32)
     _lib.call("ttdk_gemm_bf16_batched", a.data_ptr(), a.stride(1), a.stride(0), 0 if trans_a else 1, b.data_ptr(),
               b.stride(1), b.stride(0), 1 if trans_b else 0, out.data_ptr(), N, M * N,
               1 if out_dtype == torch.float32 else 0, M, N, K, Bt, _lib.stream())
+    return out
+
+
+def _check_grouped(name, t, what, cols=None):
+    """bf16 2-D operand of the grouped kernels: rows may be strided; 16-byte aligned rows."""
+    if t.dtype != torch.bfloat16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+        raise InvalidArgumentError("%s: %s must be a row-major 2-D CUDA bfloat16 tensor (got %s %s shape %s strides %s)"
+                                   % (name, what, t.dtype, t.device, tuple(t.shape), t.stride()))
+    if cols is not None and t.shape[1] != cols:
+        raise InvalidArgumentError("%s: %s must have %d columns, got shape %s" % (name, what, cols, tuple(t.shape)))
+    if t.shape[1] % 8 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        raise InvalidArgumentError("%s: %s needs a width and a row stride that are multiples of 8 and a 16-byte "
+                                   "aligned base (shape %s, row stride %d, base %% 16 = %d)"
+                                   % (name, what, tuple(t.shape), t.stride(0), t.data_ptr() % 16))
+
+
+def _check_offsets(name, offsets, E, dev):
+    if E < 1 or E > _lib.query("ttdk_grouped_gemm_max_groups"):
+        raise InvalidArgumentError("%s: the number of groups must be in [1, %d], got %d"
+                                   % (name, _lib.query("ttdk_grouped_gemm_max_groups"), E))
+    if (offsets.dtype != torch.int32 or offsets.device != dev or tuple(offsets.shape) != (E + 1,)
+            or not offsets.is_contiguous()):
+        raise InvalidArgumentError("%s: offsets must be a contiguous int32 [%d] tensor on %s (got %s %s shape %s)"
+                                   % (name, E + 1, dev, offsets.dtype, offsets.device, tuple(offsets.shape)))
+
+
+def grouped_gemm(x, w, offsets, *, out=None):
+    """y[r] = x[r] @ w[e] for the rows r of group e, in ONE launch (grouped_gemm.hip): x bf16 [M, K]
+    sorted by group, w bf16 [E, K, N] (the data gradient is the same call on dy and the
+    transposed weights), offsets int32 [E + 1] ON THE DEVICE (group e owns rows [offsets[e], offsets[e + 1]); never read
+    by the host, so the call neither syncs nor changes under a captured graph). Rows at or past
+    offsets[E] are zeros. Returns bf16 [M, N]."""
+    name = "grouped_gemm"
+    _check_grouped(name, x, "x")
+    M, K = x.shape
+    if w.dtype != torch.bfloat16 or w.device != x.device or w.dim() != 3 or not w.is_contiguous() or w.data_ptr() % 16:
+        raise InvalidArgumentError("%s: w must be a contiguous 16-byte aligned 3-D bfloat16 tensor on %s (got %s %s shape %s)"
+                                   % (name, x.device, w.dtype, w.device, tuple(w.shape)))
+    E, Kw, N = w.shape
+    if Kw != K or N % 8 or N < 8 or K < 8:
+        raise InvalidArgumentError("%s: x %s does not match w %s; K and N must be positive multiples of 8"
+                                   % (name, tuple(x.shape), tuple(w.shape)))
+    _check_offsets(name, offsets, E, x.device)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    else:
+        _check_grouped(name, out, "out", N)
+        if out.shape[0] != M:
+            raise InvalidArgumentError("%s: out must be [%d, %d], got %s" % (name, M, N, tuple(out.shape)))
+    _log("grouped_gemm", M, N, K, E)
+    _lib.call("ttdk_grouped_gemm", x.data_ptr(), x.stride(0) if M else K, w.data_ptr(), offsets.data_ptr(),
+              out.data_ptr(), out.stride(0) if M else N, M, N, K, E, _lib.stream())
+    return out
+
+
+def grouped_wgrad(x, dy, offsets, *, out=None):
+    """dw[e] = x[rows of e]^T @ dy[rows of e], fp32 [E, K, N], in ONE launch and bitwise repeatable
+    (no atomics): x bf16 [M, K], dy bf16 [M, N], offsets as in grouped_gemm. Every dw[e] is written;
+    an empty group's is zeros."""
+    name = "grouped_wgrad"
+    _check_grouped(name, x, "x")
+    _check_grouped(name, dy, "dy")
+    M, K = x.shape
+    N = dy.shape[1]
+    if dy.shape[0] != M or dy.device != x.device or K < 8 or N < 8:
+        raise InvalidArgumentError("%s: x %s and dy %s must have equal rows, one device and non-empty columns"
+                                   % (name, tuple(x.shape), tuple(dy.shape)))
+    E = offsets.numel() - 1
+    _check_offsets(name, offsets, E, x.device)
+    if out is None:
+        out = torch.empty((E, K, N), dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.device != x.device or tuple(out.shape) != (E, K, N)
+          or not out.is_contiguous() or out.data_ptr() % 16):
+        raise InvalidArgumentError("%s: out must be a contiguous 16-byte aligned float32 [%d, %d, %d] tensor on %s "
+                                   "(got %s shape %s)" % (name, E, K, N, x.device, out.dtype, tuple(out.shape)))
+    _log("grouped_wgrad", K, N, M, E)
+    _lib.call("ttdk_grouped_wgrad", x.data_ptr(), x.stride(0) if M else K, dy.data_ptr(), dy.stride(0) if M else N,
+              offsets.data_ptr(), out.data_ptr(), M, N, K, E, _lib.stream())
     return out
 
 
