@@ -441,24 +441,6 @@ class SwiGLU(Layer):
         return N.swiglu(N.dense(x, self.kernel, self.bias))
 
 
-class _Gather(torch.autograd.Function):
-    """src[idx // k] for a permutation idx of the src.shape[0] * k slots, with the inverse
-    permutation handed in: the gradient is d[inv] summed over each row's k slots, a gather too, so
-    neither direction scatters (no index_add, deterministic)."""
-
-    @staticmethod
-    def forward(ctx, src, idx, inv, k):
-        ctx.save_for_backward(inv)
-        ctx.k = k
-        return src[idx // k if k > 1 else idx]
-
-    @staticmethod
-    def backward(ctx, d):
-        (inv,) = ctx.saved_tensors
-        g = d[inv]
-        return (g.reshape(-1, ctx.k, g.shape[-1]).sum(1) if ctx.k > 1 else g), None, None, None
-
-
 class MixtureOfExperts(Layer):
     """Token-choice mixture-of-experts feed-forward over the last axis (Mixtral / Qwen-MoE block):
     an fp32 router (`router/kernel` [in, num_experts], no bias), softmax, top_k experts per token
@@ -466,7 +448,9 @@ class MixtureOfExperts(Layer):
     intermediate_size — gated: swiglu(x W_in) W_out with `experts_in/kernel` [E, in, 2 * F] (gate
     columns first); not gated: gelu(x W_in) W_out with [E, in, F] — `experts_out/kernel` [E, F, in].
     Tokens are sorted by expert on the device and both projections are one grouped matmul
-    (ttd.nn.grouped_matmul); nothing here reads the routing back to the host, no token is dropped.
+    (ttd.nn.moe_route, moe_dispatch, grouped_matmul, moe_combine: on the GPU the routing kernels for up
+    to 256 experts, top_k <= 8 and a width that is a multiple of 8, torch ops otherwise); nothing
+    here reads the routing back to the host, no token is dropped.
     `aux_loss` holds the Switch load-balancing term of the last call, E * sum_e f_e * P_e with f_e
     the share of the tokens' top_k slots routed to expert e and P_e the mean router probability
     of e; like `losses` it is part of no loss unless the caller adds it."""
@@ -500,19 +484,17 @@ class MixtureOfExperts(Layer):
         E, k = self.num_experts, self.top_k
         x2 = x.reshape(-1, x.shape[-1])
         T = x2.shape[0]
-        probs = torch.softmax(N.dense(x2.float(), self.router_kernel.float()), dim=-1)   # [T, E]
-        gate, expert = torch.topk(probs, k, dim=-1)
-        gate = gate / gate.sum(-1, keepdim=True)
-        slots = expert.reshape(-1)                        # slot t * k + j: the j-th expert of token t
-        order = torch.argsort(slots, stable=True)         # sorted row -> slot
-        inv = torch.argsort(order)                        # slot -> sorted row
-        sizes = torch.bincount(slots, minlength=E)
+        # the routing kernels on the GPU within their range (else, as on the CPU, the torch expressions)
+        fused = x2.is_cuda and N._moe_kernels_take(E, k, x2.shape[1])
+        gate, expert, probs = N.moe_route(N.dense(x2.float(), self.router_kernel.float()), k, fused=fused)
+        xs, groups, plan = N.moe_dispatch(x2, expert, E, dtype=torch.bfloat16 if fused else None, fused=fused)
+        how = {"offsets": groups} if fused else {"group_sizes": groups}
+        sizes = groups[1:] - groups[:-1] if fused else groups
         self.aux_loss = E * torch.sum(sizes.to(probs.dtype) / (T * k) * probs.mean(0))
-        h = N.grouped_matmul(_Gather.apply(x2, order, inv, k), self.experts_in_kernel, sizes)
+        h = N.grouped_matmul(xs, self.experts_in_kernel, **how)
         h = N.swiglu(h) if self.gated else N.gelu(h)
-        h = N.grouped_matmul(h, self.experts_out_kernel, sizes)
-        y = (_Gather.apply(h, inv, order, 1).reshape(T, k, -1).float() * gate.unsqueeze(-1)).sum(1)
-        return y.to(x.dtype).reshape(x.shape)
+        h = N.grouped_matmul(h, self.experts_out_kernel, **how)
+        return N.moe_combine(h, gate, plan, dtype=x.dtype, fused=fused).reshape(x.shape)
 
 
 class Embedding(Layer):

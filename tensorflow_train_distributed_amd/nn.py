@@ -26,6 +26,9 @@ accumulation) for either input dtype.
     ttd.nn.rms_norm(x, gamma); ttd.nn.swiglu(x)           # RMSNorm; silu(x[..., :I]) * x[..., I:]
     ttd.nn.group_norm(x, gamma, beta, groups=32)          # [N, *spatial, C], per-sample group statistics
     ttd.nn.grouped_matmul(x, kernels, group_sizes)        # rows sorted by expert, kernels [E, K, N]
+    gate, expert, probs = ttd.nn.moe_route(logits, top_k) # softmax, top-k experts, renormalised gates
+    xs, sizes, plan = ttd.nn.moe_dispatch(x, expert, E)   # token rows sorted by expert (k rows a token)
+    ttd.nn.moe_combine(h, gate, plan)                     # y[t] = sum_j gate[t, j] * h[row of (t, j)]
 """
 from __future__ import annotations
 
@@ -633,11 +636,11 @@ class _GroupedMatMul(torch.autograd.Function):
     the op can be captured into a graph."""
 
     @staticmethod
-    def forward(ctx, x, kernels, group_sizes):
+    def forward(ctx, x, kernels, group_sizes, offsets=None):
         from .ops import gemm as G
         xb = x.to(torch.bfloat16).contiguous()
         wb = kernels.to(torch.bfloat16).contiguous()          # [E, in, out]
-        off = F.pad(torch.cumsum(group_sizes, 0, dtype=torch.int32), (1, 0))
+        off = offsets if offsets is not None else F.pad(torch.cumsum(group_sizes, 0, dtype=torch.int32), (1, 0))
         y = G.grouped_gemm(xb, wb, off)
         ctx.save_for_backward(xb, wb, off)
         ctx.cfg = (x.dtype, kernels.dtype)
@@ -651,19 +654,32 @@ class _GroupedMatMul(torch.autograd.Function):
         d = dy.to(torch.bfloat16).contiguous()
         dx = G.grouped_gemm(d, wb.transpose(1, 2).contiguous(), off).to(xdt) if ctx.needs_input_grad[0] else None
         dw = G.grouped_wgrad(xb, d, off).to(wdt) if ctx.needs_input_grad[1] else None
-        return dx, dw, None
+        return dx, dw, None, None
 
 
-def grouped_matmul(x, kernels, group_sizes):
+def grouped_matmul(x, kernels, group_sizes=None, *, offsets=None):
     """y[r] = x[r] @ kernels[e] for the rows r of group e: x [M, K] sorted by group, kernels
     [E, K, N], group_sizes an integer tensor [E] on x's device (group e owns the group_sizes[e] rows
     after those of groups < e). Rows past group_sizes.sum() give zero output and zero gradient. The
     expert matmul of a mixture-of-experts block. GPU: the grouped MFMA kernels in bf16 with fp32
-    accumulation, K and N multiples of 8; CPU: a loop over the groups in the input dtype."""
+    accumulation, K and N multiples of 8; CPU: a loop over the groups in the input dtype.
+    offsets (keyword only, in place of group_sizes): the int32 [E + 1] table of row boundaries that
+    moe_dispatch returns on the GPU, used as it is; on the CPU its differences are the sizes."""
     if x.dim() != 2 or kernels.dim() != 3 or kernels.shape[1] != x.shape[1]:
         raise InvalidArgumentError("ttd.nn.grouped_matmul: x must be [M, K] and kernels [E, K, N], got %s and %s"
                                    % (tuple(x.shape), tuple(kernels.shape)))
     E = kernels.shape[0]
+    if offsets is not None:
+        if (group_sizes is not None or offsets.dtype != torch.int32 or tuple(offsets.shape) != (E + 1,)
+                or offsets.device != x.device):
+            raise InvalidArgumentError("ttd.nn.grouped_matmul: offsets stands in for group_sizes and must be an int32 "
+                                       "[%d] tensor on %s, got %s %s on %s" % (E + 1, x.device, offsets.dtype,
+                                                                             tuple(offsets.shape), offsets.device))
+        if _on_gpu(x, kernels):
+            return _GroupedMatMul.apply(x, kernels, None, offsets.contiguous())
+        group_sizes = offsets[1:] - offsets[:-1]
+    if group_sizes is None:
+        raise InvalidArgumentError("ttd.nn.grouped_matmul: neither group_sizes nor offsets given")
     if (group_sizes.is_floating_point() or group_sizes.is_complex() or group_sizes.dtype == torch.bool
             or tuple(group_sizes.shape) != (E,) or group_sizes.device != x.device):
         raise InvalidArgumentError("ttd.nn.grouped_matmul: group_sizes must be an integer [%d] tensor on %s, got %s %s "
@@ -679,6 +695,166 @@ def grouped_matmul(x, kernels, group_sizes):
         raise InvalidArgumentError("ttd.nn.grouped_matmul: group_sizes sum to %d, x has %d rows" % (r, x.shape[0]))
     outs.append(x.new_zeros((x.shape[0] - r, kernels.shape[2])))
     return torch.cat(outs)
+
+
+# ------------------------------------------------------------------ mixture-of-experts routing
+class _MoeRoute(torch.autograd.Function):
+    """softmax -> top-k -> renormalise in one launch, and one launch back (moe_route.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits, k):
+        from .ops import moe as M
+        probs, expert, gate = M.topk_route(logits, k)
+        ctx.save_for_backward(probs, expert, gate)
+        ctx.mark_non_differentiable(expert)
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
+        return gate, expert, probs
+
+    @staticmethod
+    def backward(ctx, dgate, _, dprobs):
+        from .ops import moe as M
+        probs, expert, gate = ctx.saved_tensors
+        return M.topk_route_bwd(probs, expert, gate, None if dgate is None else dgate.float().contiguous(),
+                                None if dprobs is None else dprobs.float().contiguous()), None
+
+
+class _GatherRows(torch.autograd.Function):
+    """src[idx // k] for a permutation idx of the src.shape[0] * k slots, with the inverse
+    permutation handed in: the gradient is d[inv] summed over each row's k slots, a gather too, so
+    neither direction scatters (no index_add, deterministic). The torch form of the dispatch."""
+
+    @staticmethod
+    def forward(ctx, src, idx, inv, k):
+        ctx.save_for_backward(inv)
+        ctx.k = k
+        return src[idx // k if k > 1 else idx]
+
+    @staticmethod
+    def backward(ctx, d):
+        (inv,) = ctx.saved_tensors
+        g = d[inv]
+        return (g.reshape(-1, ctx.k, g.shape[-1]).sum(1) if ctx.k > 1 else g), None, None, None
+
+
+class _MoeDispatch(torch.autograd.Function):
+    """xs[r] = x[order[r] // k], converted in flight; back, dx[t] = sum_j dxs[inv[t * k + j]]."""
+
+    @staticmethod
+    def forward(ctx, x, order, inv, k, dtype):
+        from .ops import moe as M
+        ctx.save_for_backward(inv)
+        ctx.cfg = (k, x.dtype)
+        return M.gather_rows(x, order, k, dtype=dtype)
+
+    @staticmethod
+    def backward(ctx, d):
+        from .ops import moe as M
+        (inv,) = ctx.saved_tensors
+        k, dt = ctx.cfg
+        return M.combine_rows(d.contiguous(), inv, k, dtype=dt), None, None, None, None
+
+
+class _MoeCombine(torch.autograd.Function):
+    """y[t] = sum_j gate[t, j] * h[inv[t * k + j]]; back, dh and dgate in one pass over dy and h."""
+
+    @staticmethod
+    def forward(ctx, h, gate, order, inv, k, dtype):
+        from .ops import moe as M
+        g = gate.float().contiguous()
+        ctx.save_for_backward(h, g, order)
+        ctx.cfg = (k, gate.dtype)
+        return M.combine_rows(h, inv, k, w=g, dtype=dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .ops import moe as M
+        h, g, order = ctx.saved_tensors
+        k, gdt = ctx.cfg
+        dh, dgate = M.gather_rows(dy.contiguous(), order, k, scale=g, h=h, dtype=h.dtype)
+        return dh, dgate.reshape(g.shape).to(gdt), None, None, None, None
+
+
+class MoePlan:
+    """The permutation of a dispatch: order int [T * k] sorted row -> slot (slot t * k + j is the
+    j-th choice of token t), inv its inverse, k choices per token."""
+    __slots__ = ("order", "inv", "k")
+
+    def __init__(self, order, inv, k):
+        self.order, self.inv, self.k = order, inv, k
+
+
+def _moe_kernels_take(num_experts, top_k, width):
+    """Whether the routing kernels serve this block: E and top_k within the router's limits and a
+    row width the 16-byte row kernels take."""
+    from .ops import moe as M
+    return num_experts <= M.max_experts() and top_k <= M.max_topk() and width % 8 == 0 and width >= 8
+
+
+def moe_route(logits, top_k, *, fused=True):
+    """The router of a token-choice mixture-of-experts block: (gate, expert, probs) of logits [T, E]
+    with probs = softmax(logits) [T, E], expert [T, top_k] the top_k experts of every token in
+    descending order and gate [T, top_k] their probabilities renormalised to sum 1. Gradients flow
+    into logits from gate and from probs (an auxiliary loss). GPU: one fp32 kernel each way
+    (moe_route.hip), expert int32, selected on the logits with ties to the lowest index, E <= 256 and
+    top_k <= 8; CPU, or fused=False: softmax, topk and a division in torch ops, expert int64."""
+    top_k = int(top_k)
+    if logits.dim() != 2 or not 1 <= top_k <= max(logits.shape[1], 1) or logits.shape[1] < 1:
+        raise InvalidArgumentError("ttd.nn.moe_route: logits must be [T, E] with 1 <= top_k <= E, got %s and top_k = %d"
+                                   % (tuple(logits.shape), top_k))
+    if fused and _on_gpu(logits):
+        return _MoeRoute.apply(logits.float(), top_k)
+    probs = torch.softmax(logits, dim=-1)
+    gate, expert = torch.topk(probs, top_k, dim=-1)
+    gate = gate / gate.sum(-1, keepdim=True)
+    return gate, expert, probs
+
+
+def moe_dispatch(x, expert, num_experts, *, dtype=None, fused=True):
+    """Sort the tokens of x [T, D] by expert [T, k] (stable: an expert's rows keep token order):
+    (xs, groups, plan) with xs [T * k, D] the row of every (token, choice) slot, groups what
+    grouped_matmul needs to cut xs — on the GPU the int32 [num_experts + 1] offsets table (pass it
+    as grouped_matmul(..., offsets=groups)), on the CPU the [num_experts] group sizes — and plan the
+    MoePlan moe_combine takes. Gradients flow into x. GPU: a counting sort and a row gather
+    (moe_route.hip), D a multiple of 8, xs in dtype (default x's: fp32 -> bf16 converts in flight);
+    ids outside [0, num_experts) sort into the rows of no group. CPU, or fused=False: argsort,
+    bincount and an index gather."""
+    E = int(num_experts)
+    if (x.dim() != 2 or expert.dim() != 2 or expert.shape[0] != x.shape[0] or expert.is_floating_point()
+            or expert.device != x.device or E < 1):
+        raise InvalidArgumentError("ttd.nn.moe_dispatch: x must be [T, D] and expert an integer [T, k] tensor on %s with "
+                                   "num_experts >= 1, got %s, %s %s on %s, %d"
+                                   % (x.device, tuple(x.shape), expert.dtype, tuple(expert.shape), expert.device, E))
+    k = expert.shape[1]
+    if fused and _on_gpu(x):
+        from .ops import moe as M
+        offsets, order, inv = M.sort_by_expert(expert.to(torch.int32).contiguous(), E)
+        return _MoeDispatch.apply(x.contiguous(), order, inv, k, dtype or x.dtype), offsets, MoePlan(order, inv, k)
+    slots = expert.reshape(-1).long()                 # slot t * k + j: the j-th expert of token t
+    order = torch.argsort(slots, stable=True)         # sorted row -> slot
+    inv = torch.argsort(order)                        # slot -> sorted row
+    sizes = torch.bincount(slots, minlength=E)
+    xs = _GatherRows.apply(x, order, inv, k)
+    return (xs if dtype is None else xs.to(dtype)), sizes, MoePlan(order, inv, k)
+
+
+def moe_combine(h, gate, plan, *, dtype=None, fused=True):
+    """y[t] = sum_j gate[t, j] * h[row of slot (t, j)]: the expert outputs h [T * k, D] in the sorted
+    order of moe_dispatch's plan, weighted and summed per token in fp32; y [T, D] float32 (dtype:
+    another output type). Gradients flow into h and gate. GPU: one kernel each way (moe_route.hip),
+    the backward forming dh and dgate in a single pass; CPU, or fused=False: index, multiply, sum."""
+    k = plan.k
+    if (h.dim() != 2 or gate.dim() != 2 or gate.shape[1] != k or gate.shape[0] * k != h.shape[0]
+            or plan.inv.shape[0] != h.shape[0] or gate.device != h.device):
+        raise InvalidArgumentError("ttd.nn.moe_combine: h must be [T * k, D] and gate [T, k] on one device for a plan of "
+                                   "%d slots with k = %d, got %s and %s" % (plan.inv.shape[0], k, tuple(h.shape),
+                                                                           tuple(gate.shape)))
+    if fused and _on_gpu(h, gate):
+        # a plan made by the torch path holds int64 indices: the kernels take int32
+        return _MoeCombine.apply(h.contiguous(), gate, plan.order.to(torch.int32), plan.inv.to(torch.int32), k,
+                                 dtype or torch.float32)
+    T = gate.shape[0]
+    y = (_GatherRows.apply(h, plan.inv.long(), plan.order.long(), 1).reshape(T, k, -1).float() * gate.unsqueeze(-1)).sum(1)
+    return y if dtype is None else y.to(dtype)
 
 
 class _BatchNorm(torch.autograd.Function):
