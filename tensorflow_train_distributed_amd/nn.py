@@ -697,6 +697,70 @@ def grouped_matmul(x, kernels, group_sizes=None, *, offsets=None):
     return torch.cat(outs)
 
 
+class _LinearXent(torch.autograd.Function):
+    """Loss of a linear layer's logits without the logits (linear_xent.hip): the forward keeps lse
+    [T], the backward recomputes the logits a bounded chunk of rows at a time."""
+
+    @staticmethod
+    def forward(ctx, x, weights, labels, bias):
+        from .ops import transformer as T
+        h = x.reshape(-1, x.shape[-1])
+        if h.stride(1) != 1:
+            h = h.contiguous()
+        w = weights if weights.stride(1) == 1 else weights.contiguous()
+        lab = labels.reshape(-1)
+        if lab.dtype != torch.int32:  # a wider label outside [0, V) must stay outside after the cast
+            lab = torch.where((lab >= 0) & (lab < weights.shape[0]), lab, -1).to(torch.int32)
+        lab = lab.contiguous()
+        b = _f32(bias)
+        loss, lse, _ = T.linear_xent_fwd(h, w, lab, b)
+        ctx.save_for_backward(h, w, lab, b, lse)
+        ctx.cfg = (x.shape, None if bias is None else bias.dtype)
+        return loss.reshape(labels.shape)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from .ops import transformer as T
+        h, w, lab, b, lse = ctx.saved_tensors
+        shp, bdt = ctx.cfg
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], b is not None and ctx.needs_input_grad[3])
+        dh, dw, db = T.linear_xent_bwd(h, w, lab, lse, dloss.reshape(-1).float().contiguous(), b, want=want)
+        return (dh.reshape(shp) if dh is not None else None, dw.to(w.dtype) if dw is not None else None, None,
+                db.to(bdt) if db is not None else None)
+
+
+def linear_cross_entropy(x, weights, labels, bias=None):
+    """Per-example softmax cross-entropy of the logits x @ weights^T + bias, which are never formed
+    as a tensor: x [..., H], weights [V, H] (the layout of tf.nn.sampled_softmax_loss's weights and of
+    a tied embedding table), integer labels [...], bias [V] or None; returns the fp32 loss [...]. A
+    label outside [0, V) marks an ignored example: loss 0 and no gradient. Gradients go to x,
+    weights and bias, each computed only when needed and returned in its input's dtype. GPU: the
+    fused kernels, bf16 x and weights with H and V multiples of 8 — anything else on the GPU is
+    refused, not run another way. CPU: the fp32 formula in torch ops."""
+    if x.dim() < 1 or weights.dim() != 2 or weights.shape[1] != x.shape[-1] or tuple(labels.shape) != tuple(x.shape[:-1]):
+        raise InvalidArgumentError("ttd.nn.linear_cross_entropy: x [..., H], weights [V, H] and labels [...] do not "
+                                   "match: %s, %s, %s" % (tuple(x.shape), tuple(weights.shape), tuple(labels.shape)))
+    V, H = weights.shape
+    if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+        raise InvalidArgumentError("ttd.nn.linear_cross_entropy: labels must be integers, got %s" % labels.dtype)
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise InvalidArgumentError("ttd.nn.linear_cross_entropy: bias must be [%d], got %s" % (V, tuple(bias.shape)))
+    if _on_gpu(x, weights, bias, labels):
+        if x.dtype != torch.bfloat16 or weights.dtype != torch.bfloat16 or H % 8 or V % 8 or H < 8 or V < 8 \
+                or x.numel() == 0:
+            raise InvalidArgumentError("ttd.nn.linear_cross_entropy on the GPU takes non-empty bfloat16 x and weights "
+                                       "with H and V positive multiples of 8, got %s %s and %s %s"
+                                       % (x.dtype, tuple(x.shape), weights.dtype, tuple(weights.shape)))
+        return _LinearXent.apply(x, weights, labels, bias)
+    z = x.float() @ weights.float().t()
+    if bias is not None:
+        z = z + bias.float()
+    lab = labels.long()
+    valid = (lab >= 0) & (lab < V)
+    zt = z.gather(-1, lab.clamp(0, V - 1).unsqueeze(-1)).squeeze(-1)
+    return torch.where(valid, torch.logsumexp(z, -1) - zt, torch.zeros((), dtype=z.dtype, device=z.device))
+
+
 # ------------------------------------------------------------------ mixture-of-experts routing
 class _MoeRoute(torch.autograd.Function):
     """softmax -> top-k -> renormalise in one launch, and one launch back (moe_route.hip)."""

@@ -537,6 +537,127 @@ def xent_vocab(logits, V, labels, gscale, *, dlogits=None, sums=None, mscale=Non
     return dlogits
 
 
+# ------------------------------------------------------------------ fused LM-head cross-entropy (linear_xent.hip)
+LINEAR_XENT_WS_BYTES = 256 << 20   # bound of the backward's bf16 [chunk_rows, V] workspace
+
+
+def _lx_check(name, h, w, labels, bias):
+    """bf16 h [T, H] and w [V, H] with strided rows, int32 labels [T], fp32 bias [V] or None."""
+    for what, t in (("h", h), ("w", w)):
+        if t.dtype != torch.bfloat16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise InvalidArgumentError("%s: %s must be a row-major 2-D CUDA bfloat16 tensor (got %s %s shape %s "
+                                       "strides %s)" % (name, what, t.dtype, t.device, tuple(t.shape), t.stride()))
+        if t.shape[1] % 8 or _ld(t) % 8 or _ld(t) < t.shape[1] or t.data_ptr() % 16:
+            raise InvalidArgumentError("%s: %s needs a width and a row stride that are multiples of 8 and a 16-byte "
+                                       "aligned base (shape %s, row stride %d, base %% 16 = %d)"
+                                       % (name, what, tuple(t.shape), _ld(t), t.data_ptr() % 16))
+    if torch.cuda.is_current_stream_capturing():
+        raise InvalidArgumentError("%s: recording into a hipGraph is not supported (a later graph replay in the same "
+                                   "process crashed after one had been recorded; the cause is not known)" % name)
+    (T, H), V = h.shape, w.shape[0]
+    if w.shape[1] != H or w.device != h.device or T < 1 or H < 8 or V < 8 or V % 8:
+        raise InvalidArgumentError("%s: h %s and w %s must be [T, H] and [V, H] on one device with T >= 1 and H, V "
+                                   "positive multiples of 8" % (name, tuple(h.shape), tuple(w.shape)))
+    if labels.dtype != torch.int32 or labels.device != h.device or tuple(labels.shape) != (T,) \
+            or not labels.is_contiguous():
+        raise InvalidArgumentError("%s: labels must be a contiguous int32 [%d] tensor on %s (got %s %s shape %s)"
+                                   % (name, T, h.device, labels.dtype, labels.device, tuple(labels.shape)))
+    if bias is not None:
+        _lx_f32(name, "bias", bias, (V,), h.device)
+    return T, H, V
+
+
+def _lx_f32(name, what, t, shape, dev):
+    if (t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous()
+            or t.data_ptr() % 16):
+        raise InvalidArgumentError("%s: %s must be a contiguous 16-byte aligned float32 %s tensor on %s (got %s %s "
+                                   "shape %s)" % (name, what, list(shape), dev, t.dtype, t.device, tuple(t.shape)))
+
+
+def linear_xent_fwd(h, w, labels, bias=None, *, splits=None):
+    """Per-row softmax cross-entropy of the logits h @ w^T + bias, which are never stored
+    (linear_xent.hip): h bf16 [T, H] (rows may be strided), w bf16 [V, H] (an embedding table as it
+    is), labels int32 [T], bias fp32 [V] or None. A label outside [0, V) marks an ignored row (loss
+    0, correct 0). Returns (loss fp32 [T], lse fp32 [T], correct int32 [T]); correct is in_top_k at
+    k = 1. splits: workgroups that share a row tile's vocabulary (default from the shapes alone);
+    the result is bitwise repeatable for a given value. Eager calls only: under hipGraph capture the
+    call is refused."""
+    name = "linear_xent_fwd"
+    T, H, V = _lx_check(name, h, w, labels, bias)
+    col_tiles = -(-V // 128)
+    if splits is None:
+        splits = _lib.query("ttdk_linear_xent_splits", T, V)
+    splits = int(splits)
+    if splits < 1 or splits > col_tiles:
+        raise InvalidArgumentError("%s: splits must be in [1, %d] for V = %d, got %d" % (name, col_tiles, V, splits))
+    dev = h.device
+    ws = torch.empty(_lib.query("ttdk_linear_xent_ws_floats", T, V, splits), dtype=torch.float32, device=dev)
+    zt, lse, loss = (torch.empty(T, dtype=torch.float32, device=dev) for _ in range(3))
+    correct = torch.empty(T, dtype=torch.int32, device=dev)
+    _lib.call("ttdk_linear_xent_fwd", h.data_ptr(), _ld(h), w.data_ptr(), _ld(w), _p(bias), labels.data_ptr(),
+              ws.data_ptr(), zt.data_ptr(), lse.data_ptr(), loss.data_ptr(), correct.data_ptr(), T, V, H, splits, _s())
+    return loss, lse, correct
+
+
+def linear_xent_chunk_rows(V):
+    """Rows per chunk of the backward: the largest multiple of 128 whose bf16 [rows, V] workspace
+    stays within LINEAR_XENT_WS_BYTES (never less than 128)."""
+    return max(128, LINEAR_XENT_WS_BYTES // (2 * V) // 128 * 128)
+
+
+def linear_xent_bwd(h, w, labels, lse, dloss, bias=None, *, chunk_rows=None, dh=None, dw=None, dbias=None,
+                    want=(True, True, True)):
+    """Gradients of linear_xent_fwd's loss for the upstream dloss fp32 [T], with the forward's lse:
+    dh bf16 [T, H], dw fp32 [V, H], dbias fp32 [V] (those of `want` = (dh, dw, dbias); None for the
+    others). The rows are walked in chunks of chunk_rows (a multiple of 128; default
+    linear_xent_chunk_rows(V)): per chunk one launch recomputes the logits and writes
+    g = (softmax - onehot) * dloss as bf16 into ONE [chunk_rows, V] workspace that every chunk
+    reuses, then dh[chunk] = g @ w, dw += g^T @ h[chunk] and dbias += column sums of g, in chunk
+    order (bitwise repeatable for a given chunk_rows). Ignored rows give zeros."""
+    from . import gemm as G
+    from . import kernels as K
+    name = "linear_xent_bwd"
+    T, H, V = _lx_check(name, h, w, labels, bias)
+    dev = h.device
+    _lx_f32(name, "lse", lse, (T,), dev)
+    _lx_f32(name, "dloss", dloss, (T,), dev)
+    if chunk_rows is None:
+        chunk_rows = linear_xent_chunk_rows(V)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 128 or chunk_rows % 128:
+        raise InvalidArgumentError("%s: chunk_rows must be a positive multiple of 128, got %d" % (name, chunk_rows))
+    want_dh, want_dw, want_db = want
+    if want_dh:
+        if dh is None:
+            dh = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        elif (dh.dtype != torch.bfloat16 or dh.device != dev or tuple(dh.shape) != (T, H) or dh.stride(1) != 1
+              or _ld(dh) < H):
+            raise InvalidArgumentError("%s: dh must be a row-major bfloat16 [%d, %d] tensor on %s" % (name, T, H, dev))
+    if want_dw:
+        if dw is None:
+            dw = torch.empty((V, H), dtype=torch.float32, device=dev)
+        else:
+            _lx_f32(name, "dw", dw, (V, H), dev)
+    if want_db:
+        if dbias is None:
+            dbias = torch.empty(V, dtype=torch.float32, device=dev)
+        else:
+            _lx_f32(name, "dbias", dbias, (V,), dev)
+    ws = torch.empty((min(chunk_rows, T), V), dtype=torch.bfloat16, device=dev)
+    for r0 in range(0, T, chunk_rows):
+        rows = min(chunk_rows, T - r0)
+        g = ws[:rows]
+        _lib.call("ttdk_linear_xent_grad", h.data_ptr(), _ld(h), w.data_ptr(), _ld(w), _p(bias), labels.data_ptr(),
+                  lse.data_ptr(), dloss.data_ptr(), g.data_ptr(), T, r0, rows, V, H, _s())
+        if want_dh:
+            G.gemm(g, w, out=dh[r0:r0 + rows])
+        if want_dw:
+            G.gemm(g, h[r0:r0 + rows], trans_a=True, out=dw, out_dtype=torch.float32, beta=1 if r0 else 0)
+        if want_db:
+            K.colsum(g, out=dbias, beta=1 if r0 else 0)
+    return (dh if want_dh else None), (dw if want_dw else None), (dbias if want_db else None)
+
+
 def dact(dy, aux, kind, out=None):
     """dy * act'(aux): kind 0 = tanh-GELU (aux = pre-activation), 1 = tanh (aux = tanh output)."""
     out = out if out is not None else torch.empty_like(dy)
